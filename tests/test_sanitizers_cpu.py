@@ -19,12 +19,16 @@ NAME = {0: "MNT4753", 1: "MNT6753"}
 def san():
     r = subprocess.run(["make", "asan", "tsan"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
-    return {k: os.path.join(ROOT, "build", "san", f"main_hip_{k}") for k in ("asan", "tsan")}
+    exe = {k: os.path.join(ROOT, "build", "san", f"main_hip_{k}") for k in ("asan", "tsan")}
+    # the commands that start them.  ThreadSanitizer's shadow layout admits only the address ranges of up to 28 bits of mmap
+    # randomisation; on kernels that use more it stops at startup ("unexpected memory mapping"), so its binary runs with address
+    # randomisation off for that one process (setarch -R: the ADDR_NO_RANDOMIZE personality, no host setting changes)
+    return {"asan": [exe["asan"]], "tsan": ["setarch", os.uname().machine, "-R", exe["tsan"]]}
 
 
 def run(exe, args, expect_rc=0, leaks=1):
     env = dict(os.environ, ASAN_OPTIONS=f"detect_leaks={leaks}:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1", TSAN_OPTIONS="halt_on_error=1")
-    r = subprocess.run([exe] + args, capture_output=True, text=True, env=env, timeout=600)
+    r = subprocess.run(exe + args, capture_output=True, text=True, env=env, timeout=600)
     assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
     assert r.returncode == expect_rc, (r.returncode, r.stderr[-2000:])
     return r
@@ -53,7 +57,7 @@ def test_compute_h_spread_over_devices_clean_under_sanitizers(san, kind, tmp_pat
         for n_dev, flags in ((2, []), (3, []), (5, ["--repeat", "2"]), (8, ["--ref-order"]), (2, ["--unfused-h", "--unfused-c"]), (3, ["--ref-order", "--unfused-h"]),
                              (4, ["--unfused-c", "--h-last"]), (3, ["--ref-order", "--touch-all"])):
             env = dict(os.environ, MNT753_TRACE="1", ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1", TSAN_OPTIONS="halt_on_error=1")
-            r = subprocess.run([san[kind], NAME[curve], "compute", params, inp, out, "--gpus", str(n_dev)] + flags, capture_output=True, text=True, env=env, timeout=600)
+            r = subprocess.run([*san[kind], NAME[curve], "compute", params, inp, out, "--gpus", str(n_dev)] + flags, capture_output=True, text=True, env=env, timeout=600)
             assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
             if "--unfused-h" not in flags:
                 assert f"compute_H over devices 0 / 1 / {2 if n_dev > 2 else 0}" in r.stderr, r.stderr[-800:]
@@ -69,7 +73,7 @@ def test_peer_access_requested_for_every_ordered_pair(san, tmp_path):
     out = str(tmp_path / "o")
     for n_dev in range(2, 9):
         env = dict(os.environ, MNT753_TRACE="1", ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-        r = subprocess.run([san["asan"], "MNT6753", "compute", params, inp, out, "--gpus", str(n_dev)], capture_output=True, text=True, env=env, timeout=600)
+        r = subprocess.run([*san["asan"], "MNT6753", "compute", params, inp, out, "--gpus", str(n_dev)], capture_output=True, text=True, env=env, timeout=600)
         assert r.returncode == 0 and "Sanitizer" not in r.stderr, r.stderr[-3000:]
         for a in range(n_dev):
             for b in range(n_dev):
@@ -77,7 +81,7 @@ def test_peer_access_requested_for_every_ordered_pair(san, tmp_path):
                     assert f"stub: peer access requested {a} -> {b}\n" in r.stderr, (n_dev, a, b)
                     assert f"mnt753: device {a} reads device {b}: same GPU" in r.stderr, (n_dev, a, b)
         assert r.stderr.count("stub: peer access requested") == n_dev * (n_dev - 1)
-    r = subprocess.run([san["asan"], "MNT6753", "compute", params, inp, out], capture_output=True, text=True, env=dict(os.environ, MNT753_TRACE="1"), timeout=600)
+    r = subprocess.run([*san["asan"], "MNT6753", "compute", params, inp, out], capture_output=True, text=True, env=dict(os.environ, MNT753_TRACE="1"), timeout=600)
     assert r.returncode == 0 and "peer access" not in r.stderr
 
 
@@ -89,7 +93,7 @@ def test_fold_over_the_exchange_clean_under_sanitizers(san, kind, tmp_path):
     out = str(tmp_path / "o")
     for n_dev, extra_env, expect in ((1, {}, "over RCCL"), (3, {}, "over RCCL"), (8, {}, "over RCCL"), (2, {"MNT753_STUB_NO_RCCL": "1"}, "folded on the host")):
         env = dict(os.environ, MNT753_TRACE="1", ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1", TSAN_OPTIONS="halt_on_error=1", **extra_env)
-        r = subprocess.run([san[kind], "MNT4753", "compute", params, inp, out, "--gpus", str(n_dev), "--fold", "rccl", "--repeat", "2"], capture_output=True, text=True, env=env, timeout=600)
+        r = subprocess.run([*san[kind], "MNT4753", "compute", params, inp, out, "--gpus", str(n_dev), "--fold", "rccl", "--repeat", "2"], capture_output=True, text=True, env=env, timeout=600)
         assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
         assert expect in r.stderr, r.stderr[-800:]
     r = run(san[kind], ["MNT4753", "compute", params, inp, out, "--gpus", "2", "--fold", "host"])
@@ -102,7 +106,7 @@ def test_resident_job_feed_clean_under_sanitizers(san, kind, tmp_path):
     params, inp, _ = G.e2e_paths(1)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", TSAN_OPTIONS="halt_on_error=1")
     feed = f"{inp} {tmp_path / 'a'}\n/nonexistent {tmp_path / 'b'}\n{inp} {tmp_path / 'c'}\n"
-    r = subprocess.run([san[kind], "MNT6753", "compute", params, inp, str(tmp_path / "o"), "--serve", "--quiet", "--gpus", "2"], input=feed, capture_output=True,
+    r = subprocess.run([*san[kind], "MNT6753", "compute", params, inp, str(tmp_path / "o"), "--serve", "--quiet", "--gpus", "2"], input=feed, capture_output=True,
                        text=True, env=env, timeout=600)
     assert r.returncode == 0 and "Sanitizer" not in r.stderr, r.stderr[-2000:]
     lines = r.stdout.strip().splitlines()
@@ -126,7 +130,7 @@ def test_one_shot_policy_reaches_the_c_abi(san, tmp_path):
     out = str(tmp_path / "o")
     def modes(flags, extra_env=None):
         env = dict(os.environ, MNT753_STUB_LOG="1", ASAN_OPTIONS="detect_leaks=1", **(extra_env or {}))
-        r = subprocess.run([san["asan"], "MNT6753", "compute", params, inp, out] + flags, capture_output=True, text=True, env=env, timeout=600)
+        r = subprocess.run([*san["asan"], "MNT6753", "compute", params, inp, out] + flags, capture_output=True, text=True, env=env, timeout=600)
         assert r.returncode == 0 and "Sanitizer" not in r.stderr, r.stderr[-2000:]
         first = [l for l in r.stderr.splitlines() if l.startswith("stub: window table mode")]
         return (first[0].rsplit(" ", 1)[1] if first else None), r.stdout
@@ -148,7 +152,7 @@ def test_self_test_is_run_once_and_is_fatal(san, tmp_path):
     out = str(tmp_path / "o")
     def go(extra):
         env = dict(os.environ, MNT753_STUB_LOG="1", ASAN_OPTIONS="detect_leaks=0", **extra)
-        return subprocess.run([san["asan"], "MNT4753", "compute", params, inp, out, "--repeat", "2"], capture_output=True, text=True, env=env, timeout=600)
+        return subprocess.run([*san["asan"], "MNT4753", "compute", params, inp, out, "--repeat", "2"], capture_output=True, text=True, env=env, timeout=600)
     r = go({})
     assert r.returncode == 0 and r.stderr.count("stub: self-test level 1 curve 0") == 1, r.stderr[-800:]
     r = go({"MNT753_SELFTEST": "0"})
