@@ -393,6 +393,8 @@ struct Mnt6G2S {
 template <class C> struct SplitOf { using type = void; };
 template <> struct SplitOf<Mnt4G2> { using type = Mnt4G2S; };
 template <> struct SplitOf<Mnt6G2> { using type = Mnt6G2S; };
+// the configuration the point kernels of group C run with: its lane-split configuration if it has one, else C itself
+template <class C> using PointCfg = std::conditional_t<std::is_void<typename SplitOf<C>::type>::value, C, typename SplitOf<C>::type>;
 
 template <class F, class = void> struct has_sqr : std::false_type {};
 template <class F> struct has_sqr<F, std::enable_if_t<F::HAS_SQR>> : std::true_type {};

@@ -1,5 +1,6 @@
 // The MSM part of the C ABI (include/mnt753_hip.h): dispatch to the per-group instantiations.
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -7,18 +8,34 @@
 #include <unordered_set>
 #include "common_host.hpp"
 #include "msm_api.hpp"
+#include "msm_knobs.hpp"
 #include "msm_types.hpp"
 
 namespace mnt753 {
-int g_window_bits_override = 0;
-int g_force_pair_levels = -1, g_force_irr_levels = -1;
 PairPool g_pair_pool[PAIR_POOL_DEVICES];
-int g_window_table_mode = 1;   // mnt753_msm_set_window_table: 1 = tables for base sets of 4096 points and more, 0 = none
-float g_last_timing[5] = {0, 0, 0, 0, 0};
-int g_last_plan[4] = {0, 0, 0, 0};
-int g_last_pair_levels = 0;
-int g_last_irr_levels = 0;
+MsmLastRun g_last_run;
+namespace {
+std::atomic<int> g_window_bits_override{0};   // mnt753_msm_set_window_bits: 0 = by size
+std::atomic<int> g_window_table_mode{1};      // mnt753_msm_set_window_table: 1 = tables for base sets of 4096 points and more, 0 = none
+}  // namespace
+
+MsmKnobs msm_knobs() {
+  MsmKnobs k;
+  k.window_bits = g_window_bits_override.load();
+  k.table = g_window_table_mode.load() != 0;
+  if (const char* e = getenv("MNT753_MSM_PRECOMP")) k.precomp = atoi(e) != 0;
+  if (const char* e = getenv("MNT753_MSM_TABLE_BITS")) { int v = atoi(e); if (v >= 8 && v <= 22) k.table_bits = v; }   // tools/experiments/window_sweep.sh
+  if (const char* e = getenv("MNT753_MSM_TMIN")) { int v = atoi(e); if (v >= 1 && v <= 4096) k.t_min = (uint32_t)v; }
+  if (const char* e = getenv("MNT753_MSM_SORT")) {
+    k.sort = !strcmp(e, "atomic") ? SORT_ATOMIC : SORT_PART;
+    k.sort_generic = !strcmp(e, "generic");
+  }
+  if (const char* e = getenv("MNT753_MSM_PAIR")) { int v = atoi(e); k.pair = v < 0 ? 0 : (v > 6 ? 6 : v); }
+  if (const char* e = getenv("MNT753_MSM_IRR")) { int v = atoi(e); k.irr = v < 0 ? 0 : (v > 8 ? 8 : v); }
+  if (const char* e = getenv("MNT753_EDGE_FLOW_NODES")) { k.edge_flow_set = true; k.edge_flow_nodes = strtoull(e, nullptr, 10); }
+  return k;
 }
+}  // namespace mnt753
 using namespace mnt753;
 
 namespace {
@@ -38,10 +55,7 @@ hipError_t create_msm_stream(hipStream_t* s, int) {
 }
 }  // namespace
 
-extern "C" {
-
-
-int mnt753_bases_create(int curve, int group, const uint64_t* affine, int on_device, size_t n, mnt753_bases** out) {
+int mnt753::bases_create(int curve, int group, const uint64_t* affine, int on_device, size_t n, const MsmKnobs& knobs, mnt753_bases** out) {
   if (!out || (n && !affine) || curve < 0 || curve > 1 || (group != MNT753_G1 && group != MNT753_G2)) return set_error(MNT753_EINVAL, "bases_create: bad argument");
   if (int rc = require_device()) return rc;
   mnt753_bases* b = new (std::nothrow) mnt753_bases();
@@ -49,8 +63,8 @@ int mnt753_bases_create(int curve, int group, const uint64_t* affine, int on_dev
   b->curve = curve; b->group = group; b->n = n;
   b->device = current_physical_device();
   int rc;
-  if (curve == MNT753_CURVE_MNT4753) rc = group == MNT753_G1 ? bases_create_mnt4g1(b, affine, on_device, n) : bases_create_mnt4g2(b, affine, on_device, n);
-  else rc = group == MNT753_G1 ? bases_create_mnt6g1(b, affine, on_device, n) : bases_create_mnt6g2(b, affine, on_device, n);
+  if (curve == MNT753_CURVE_MNT4753) rc = group == MNT753_G1 ? bases_create_mnt4g1(b, affine, on_device, n, knobs) : bases_create_mnt4g2(b, affine, on_device, n, knobs);
+  else rc = group == MNT753_G1 ? bases_create_mnt6g1(b, affine, on_device, n, knobs) : bases_create_mnt6g2(b, affine, on_device, n, knobs);
   if (rc) { mnt753_bases_free(b); return rc; }
   // the base set's own stream for mnt753_msm_start (creating a stream costs ~8 ms: do it here, at parameter-load time)
   if (create_msm_stream(&b->own_stream, group) != hipSuccess) b->own_stream = nullptr;
@@ -59,6 +73,12 @@ int mnt753_bases_create(int curve, int group, const uint64_t* affine, int on_dev
   { std::lock_guard<std::mutex> l(g_sets_mu); g_sets.insert(b); ++pair_pool_of(b).refs; b->registered = 1; }
   *out = b;
   return 0;
+}
+
+extern "C" {
+
+int mnt753_bases_create(int curve, int group, const uint64_t* affine, int on_device, size_t n, mnt753_bases** out) {
+  return bases_create(curve, group, affine, on_device, n, msm_knobs(), out);
 }
 
 int mnt753_bases_free(mnt753_bases* b) {
@@ -156,31 +176,23 @@ int mnt753_msm_finish(mnt753_bases* b, uint64_t* out_projective) {
   return b->group == MNT753_G1 ? msm_finish_mnt6g1(b, out_projective) : msm_finish_mnt6g2(b, out_projective);
 }
 
-int mnt753_msm_set_window_table(int mode) {
-  const int old = g_window_table_mode;
-  g_window_table_mode = mode != 0 ? 1 : 0;
-  return old;
-}
+int mnt753_msm_set_window_table(int mode) { return g_window_table_mode.exchange(mode != 0 ? 1 : 0); }
 
-int mnt753_msm_set_window_bits(int c) {
-  int old = g_window_bits_override;
-  g_window_bits_override = (c >= 2 && c <= 22) ? c : 0;
-  return old;
-}
+int mnt753_msm_set_window_bits(int c) { return g_window_bits_override.exchange((c >= 2 && c <= 22) ? c : 0); }
 
 
 int mnt753_msm_last_timing(float out_ms[5]) {
   if (!out_ms) return set_error(MNT753_EINVAL, "msm_last_timing: null");
-  memcpy(out_ms, g_last_timing, sizeof(g_last_timing));
+  memcpy(out_ms, g_last_run.timing, sizeof(g_last_run.timing));
   return 0;
 }
 
-int mnt753_msm_last_pair_levels(void) { return g_last_pair_levels; }
-int mnt753_msm_last_irr_levels(void) { return g_last_irr_levels; }
+int mnt753_msm_last_pair_levels(void) { return g_last_run.pair_levels; }
+int mnt753_msm_last_irr_levels(void) { return g_last_run.irr_levels; }
 
 int mnt753_msm_last_plan(int out[4]) {
   if (!out) return set_error(MNT753_EINVAL, "msm_last_plan: null");
-  memcpy(out, g_last_plan, sizeof(g_last_plan));
+  memcpy(out, g_last_run.plan, sizeof(g_last_run.plan));
   return 0;
 }
 

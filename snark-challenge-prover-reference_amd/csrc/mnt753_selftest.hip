@@ -24,10 +24,9 @@
 
 #include "common_host.hpp"
 #include "mnt753_selftest_data.h"
+#include "msm_api.hpp"
+#include "msm_types.hpp"
 
-namespace mnt753 {
-extern int g_force_pair_levels, g_force_irr_levels, g_window_table_mode;
-}
 using namespace mnt753;
 
 namespace {
@@ -81,25 +80,24 @@ int msm_checks(Ctx& c, int curve, int group, int level) {
   if (int rc = mnt753_synth_scalars(curve, MNT753_SELFTEST_SEED_MSM + 16 * curve + group, n, sc.data())) return rc;
   memset(&sc[12 * MNT753_SELFTEST_ZERO_AT], 0, 96);
   memcpy(&sc[12 * MNT753_SELFTEST_ONE_AT], ONE[curve], 96);
-  struct Restore {
-    int pair = g_force_pair_levels, irr = g_force_irr_levels, table = g_window_table_mode;
-    ~Restore() { g_force_pair_levels = pair; g_force_irr_levels = irr; g_window_table_mode = table; }
-  } restore;
   for (int pass = 0; pass < (level >= 2 ? 2 : 1); ++pass) {
-    g_window_table_mode = pass == 0 ? 1 : 2;          // 1: no table for a set this small; 2: a table whatever the size (this file only)
+    MsmKnobs knobs = msm_knobs();
+    knobs.table = true;                 // pass 0: no table for a set this small
+    knobs.table_any_size = pass == 1;   // pass 1: a table whatever the size
     mnt753_bases* bs = nullptr;
-    if (int rc = mnt753_bases_create(curve, group, pts.data(), 0, n, &bs)) return rc;
+    if (int rc = bases_create(curve, group, pts.data(), 0, n, knobs, &bs)) return rc;
     int rc = 0;
     for (int forced = 0; forced < 2 && rc == 0; ++forced) {
-      g_force_pair_levels = forced ? 1 : -1;
-      g_force_irr_levels = forced ? 1 : -1;
+      // the level kernels of the large sets, on this set only: one regular and one irregular level
+      bs->force_pair_levels = bs->force_irr_levels = forced ? 1 : -1;
       rc = mnt753_msm(bs, 0, sc.data(), 0, n, proj.data(), nullptr);
+      if (rc == 0 && forced && (bs->run_plan.pair_levels < 1 || bs->run_plan.irr_levels < 1))
+        rc = set_error(MNT753_ESELFTEST, "self-test: the MSM with batched-affine levels ran without them (no room for their buffers?)");
       if (rc == 0) rc = mnt753_point_to_affine(curve, group, proj.data(), aff.data());
       if (rc == 0)
         c.same(aff.data(), g.msm, aw, pass ? (forced ? "256-point MSM over a window table, batched-affine levels" : "256-point MSM over a window table")
                                            : (forced ? "256-point MSM with batched-affine levels against libff's multi_exp" : "256-point MSM against libff's multi_exp"), curve, group);
     }
-    g_force_pair_levels = g_force_irr_levels = -1;
     (void)mnt753_bases_free(bs);
     if (rc) return rc;
   }

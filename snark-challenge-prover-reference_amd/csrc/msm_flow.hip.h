@@ -375,7 +375,7 @@ __device__ __forceinline__ void flow_add(uint32_t* grp, uint32_t l, const uint32
   } else if (same) {
     // equal points: the VM's addition (it turns into its doubling), on the lanes of the group that form one logical lane of the VM's
     // configuration -- a pair starts on an even lane, a triple on a multiple of three (curve753.hip.h)
-    using V = std::conditional_t<std::is_void<typename SplitOf<C>::type>::value, C, typename SplitOf<C>::type>;
+    using V = PointCfg<C>;
     constexpr uint32_t VL = (uint32_t)V::F::LANES;
     const uint32_t lane = threadIdx.x & 63u, base = lane - l;
     const uint32_t first = VL == 3u ? ((base + 2u) / 3u) * 3u : base;

@@ -14,28 +14,18 @@
 #include "common_host.hpp"
 #include "host_field.hpp"
 #include "msm_kernels.hip.h"
+#include "msm_knobs.hpp"
 #include "msm_types.hpp"
 #include "msm_sort.hpp"
 #include "mnt753_generators.h"
 
 using namespace mnt753;
 
-namespace mnt753 {
-extern int g_window_bits_override;
-extern int g_window_table_mode;
-// (PairPool, the device's pooled buffers of the batched-affine levels: msm_types.hpp)
-extern int g_force_pair_levels, g_force_irr_levels;   // >= 0: mnt753_self_test puts the level kernels onto its small sets (as MNT753_MSM_PAIR / _IRR do for the tests)
-extern float g_last_timing[5];
-extern int g_last_plan[4];
-extern int g_last_pair_levels;
-extern int g_last_irr_levels;
-}
 namespace {
 
-
 // window size: minimise  N*W (bucket adds)  +  ~3 * nb * W (reduction adds, incl. the k0*run tail)
-int pick_window_bits(size_t n) {
-  if (g_window_bits_override > 0) return g_window_bits_override;   // mnt753_msm_set_window_bits (tests)
+int pick_window_bits(size_t n, const MsmKnobs& knobs) {
+  if (knobs.window_bits > 0) return knobs.window_bits;   // mnt753_msm_set_window_bits (tests)
   int best = 2; double best_cost = 1e300;
   for (int c = 2; c <= 20; ++c) {
     double W = (754 + c - 1) / c;
@@ -78,10 +68,10 @@ inline uint32_t machine_lanes(int lanes_per_point) {
 }
 // lanes_per_point: threads that share one point in the point kernels (1, or 2 / 3 with the lane-split G2 fields); the
 // machine holds 65536 threads at one wave per SIMD, i.e. 65536 / lanes_per_point points at a time
-MsmPlan make_plan(size_t n, int pre_c, int lanes_per_point = 1) {
+MsmPlan make_plan(size_t n, int pre_c, int lanes_per_point, const MsmKnobs& knobs) {
   MsmPlan p;
-  p.pre = pre_c > 0 && g_window_bits_override == 0;
-  p.c = p.pre ? pre_c : pick_window_bits(n);
+  p.pre = pre_c > 0 && knobs.window_bits == 0;
+  p.c = p.pre ? pre_c : pick_window_bits(n, knobs);
   p.W = (754 + p.c - 1) / p.c;
   p.nb = 1u << (p.c - 1);
   p.n_sets = p.pre ? 1u : (uint32_t)p.W;
@@ -97,9 +87,7 @@ MsmPlan make_plan(size_t n, int pre_c, int lanes_per_point = 1) {
   // sweep with the tree merge (profiles/r04/small_msm_sweep.txt, MNT6753 G1): 2^12 points 1.96 / 1.62 / 1.61 ms at T = 16 / 8 / 4,
   // 2^13 points 1.99 / 1.80 / 1.81; from 2^14 points on the natural T is above the floor.  MNT753_MSM_TMIN overrides: the tests use it
   // to make buckets span hundreds of lanes (trees ten levels deep in the edge merge).
-  uint64_t t_min = 8;
-  if (const char* e = getenv("MNT753_MSM_TMIN")) { int v = atoi(e); if (v >= 1 && v <= 4096) t_min = (uint64_t)v; }
-  if (T < t_min) T = t_min;
+  if (T < knobs.t_min) T = knobs.t_min;
   p.T = (uint32_t)T;
   p.n_lanes = (uint32_t)((entries + T - 1) / T);
   if (p.n_lanes == 0) p.n_lanes = 1;
@@ -113,26 +101,12 @@ MsmPlan make_plan(size_t n, int pre_c, int lanes_per_point = 1) {
   return p;
 }
 
-}  // namespace
-
-
-namespace {
-
-template <class C>
-int proj_w() { return proj_words<C>(); }
-
-// Lane-split point kernels (FieldFp2S / FieldFp3S instantiations) for the groups that have a split configuration (G2 of both
+// Lane-split point kernels (FieldFp2S / FieldFp3S instantiations, PointCfg) for the groups that have a split configuration (G2 of both
 // curves).  (The one-lane-per-point G2 kernels -- Karatsuba through one multiplier, 1.7-3.8 KB of scratch per lane, 1.8x slower -- left
 // the product in round 5; the test library still runs the one-lane forms of the group law against the reference's vectors.)
+// threads per point in the point kernels of group C
 template <class C>
-constexpr bool use_split_acc() { return !std::is_void<typename SplitOf<C>::type>::value; }
-// threads per point in the point kernels of group C under the current settings
-template <class C>
-int point_lanes() {
-  using CS = typename SplitOf<C>::type;
-  if constexpr (std::is_void<CS>::value) return 1;
-  else return CS::F::LANES;
-}
+constexpr int point_lanes() { return PointCfg<C>::F::LANES; }
 void free_pair_ws(mnt753_bases* b) {
   // (d_pairpts, d_sorted2, d_pair_ws belong to the device's PairPool: only forgotten here)
   void* ptrs[] = {b->d_fix, b->d_gen, b->d_irr_offs[0], b->d_irr_offs[1], b->d_irr_src, b->d_irr_blocks};
@@ -166,13 +140,12 @@ void free_ws(mnt753_bases* b) {
 // the partition passes took the window width as a template parameter).  MNT753_MSM_SORT=atomic / part overrides (the tests run both
 // stages on small and large inputs), =generic also keeps the partition passes on the kernels that read the width at run time.
 // (rocPRIM's radix sort, the stage of round 2 -- 1.33 ms against 0.92 -- left the product in round 5.)
-enum SortMode { SORT_ATOMIC = 0, SORT_PART = 2 };
-inline SortMode sort_mode(uint64_t entries) {
-  if (const char* e = getenv("MNT753_MSM_SORT")) return !strcmp(e, "atomic") ? SORT_ATOMIC : SORT_PART;
+inline SortMode sort_mode(uint64_t entries, const MsmKnobs& knobs) {
+  if (knobs.sort != SORT_BY_SIZE) return knobs.sort;
   return entries >= ((uint64_t)1 << 20) ? SORT_PART : SORT_ATOMIC;
 }
 template <class C>
-int ensure_ws(mnt753_bases* b, size_t n, const MsmPlan& p) {
+int ensure_ws(mnt753_bases* b, size_t n, const MsmPlan& p, const MsmKnobs& knobs) {
   // entries of the sorted list: every bucket padded to a multiple of 2^pair_levels
   const size_t sorted_need = (size_t)p.W * n + (size_t)p.n_buckets * (((size_t)1 << p.pair_levels) - 1);
   if (b->ws_n >= n && b->ws_plan.c == p.c && b->ws_plan.pre == p.pre && b->ws_plan.T == p.T && b->ws_plan.L == p.L && b->ws_plan.n_lanes >= p.n_lanes &&
@@ -189,7 +162,7 @@ int ensure_ws(mnt753_bases* b, size_t n, const MsmPlan& p) {
   HIP_TRY(hipMalloc(&b->d_total, sizeof(uint32_t) * 4));
   HIP_TRY(hipMalloc(&b->d_sorted, sizeof(uint32_t) * sorted_need));
   b->sorted_cap = sorted_need;
-  if (sort_mode((uint64_t)p.W * n) == SORT_PART) {
+  if (sort_mode((uint64_t)p.W * n, knobs) == SORT_PART) {
     // (key, value) buffers of the two-level counting sort: failing to get them only falls back to the histogram-atomic sort
     if (hipMalloc(&b->d_keys_out, sizeof(uint32_t) * (size_t)p.W * n) != hipSuccess || hipMalloc(&b->d_vals_out, sizeof(uint32_t) * (size_t)p.W * n) != hipSuccess ||
         hipMalloc(&b->d_part_ws, sizeof(uint32_t) * msm_sort_partition_ws_words()) != hipSuccess) {
@@ -216,17 +189,17 @@ int ensure_ws(mnt753_bases* b, size_t n, const MsmPlan& p) {
   return 0;
 }
 
-template <class C> MsmPlan plan_for(const mnt753_bases* b, size_t n);
-template <class C> int ensure_pair_ws_for(mnt753_bases* b, const MsmPlan& p, size_t n);
+template <class C> MsmPlan plan_for(const mnt753_bases* b, size_t n, const MsmKnobs& knobs);
+template <class V, class C> int ensure_pair_ws(mnt753_bases* b, const MsmPlan& p, size_t n);
 
 template <class C>
-int bases_create_t(mnt753_bases* b, const uint64_t* affine, int on_device, size_t n) {
+int bases_create_t(mnt753_bases* b, const uint64_t* affine, int on_device, size_t n, const MsmKnobs& knobs) {
   const size_t wire_bytes = n * 2 * wire_coord_words<C>() * 4;
   // window table: on by default for base sets large enough to amortise it over the proofs of a resident prover; a one-proof process
   // turns it off for the sets it creates (mnt753_msm_set_window_table(0): a table costs 0.33 s per 2^20 G1 points to build and saves
   // 20 ms per MSM); MNT753_MSM_PRECOMP=0 / 1 overrides both
-  bool want_table = (n >= 4096 && g_window_table_mode != 0) || (n > 0 && g_window_table_mode == 2);   // 2: mnt753_self_test, level 2
-  if (const char* e = getenv("MNT753_MSM_PRECOMP")) want_table = atoi(e) != 0 && n > 0;
+  bool want_table = (n >= 4096 && knobs.table) || (n > 0 && knobs.table_any_size);
+  if (knobs.precomp >= 0) want_table = knobs.precomp != 0 && n > 0;
   int pc = 0, pW = 1;
   if (want_table) {
     // floors (and, for Fq3, the one width its sizes ever want) from the sweep: the bucket count at which one round of lanes holds
@@ -237,7 +210,7 @@ int bases_create_t(mnt753_bases* b, const uint64_t* affine, int on_device, size_
     if (C::F::DEG == 1) pc = pick_precomp_bits(n, 8.0, n <= 4096 ? 14 : 18);
     else if (C::F::DEG == 2) pc = pick_precomp_bits(n, 8.0, n >= ((size_t)1 << 16) ? 18 : 2);
     else pc = n <= ((size_t)1 << 15) ? 14 : pick_precomp_bits(n, 8.0, 2);
-    if (const char* e = getenv("MNT753_MSM_TABLE_BITS")) { int v = atoi(e); if (v >= 8 && v <= 22) pc = v; }   // tools/experiments/window_sweep.sh
+    if (knobs.table_bits) pc = knobs.table_bits;
     pW = (754 + pc - 1) / pc;
     if ((uint64_t)pW * n >= 0x7fffffffull) { want_table = false; pc = 0; pW = 1; }   // row index must fit 31 bits
   }
@@ -268,13 +241,10 @@ int bases_create_t(mnt753_bases* b, const uint64_t* affine, int on_device, size_
     HIP_TRY(hipMalloc(&ztmp, sizeof(uint32_t) * EW * tile * (size_t)pW));
     HIP_TRY(hipMalloc(&ptmp, sizeof(uint32_t) * EW * tile * (size_t)pW));
     // the doubling chains run on the configuration the point kernels use: two / three lanes per point for G2
-    using CS = typename SplitOf<C>::type;
+    using V = PointCfg<C>;
     for (size_t i0 = 0; i0 < n; i0 += tile) {
       const size_t cnt = std::min(tile, n - i0);
-      if constexpr (!std::is_void<CS>::value)
-        hipLaunchKernelGGL((k_precompute_windows<CS>), dim3(blocks_for<typename CS::F>(cnt)), dim3(256), 0, 0, b->d_aff, b->d_inf, ztmp, ptmp, n, i0, cnt, pc, pW);
-      else
-        hipLaunchKernelGGL((k_precompute_windows<C>), dim3(blocks_for<typename C::F>(cnt)), dim3(256), 0, 0, b->d_aff, b->d_inf, ztmp, ptmp, n, i0, cnt, pc, pW);
+      hipLaunchKernelGGL((k_precompute_windows<V>), dim3(blocks_for<typename V::F>(cnt)), dim3(256), 0, 0, b->d_aff, b->d_inf, ztmp, ptmp, n, i0, cnt, pc, pW);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
@@ -289,17 +259,17 @@ int bases_create_t(mnt753_bases* b, const uint64_t* affine, int on_device, size_
   // points without a table (43 GB for the 3 x 2^20 points of H | L | B1), which the driver hands over at ~30 GB/s -- 1.5 s of a
   // parameter load measured in round 6, and as much again inside the first proof when the memory had just been another process's --
   // to save ~0.05 s on the one proof that will ever run over the set.
-  if (g_window_table_mode == 0 && !want_table) b->no_pair = 1;
+  if (!knobs.table && !want_table) b->no_pair = 1;
   {
-    MsmPlan p = plan_for<C>(b, n);
-    if (p.pair_levels > 0 && ensure_pair_ws_for<C>(b, p, n) != 0) {
+    MsmPlan p = plan_for<C>(b, n, knobs);
+    if (p.pair_levels > 0 && ensure_pair_ws<PointCfg<C>, C>(b, p, n) != 0) {
       // not enough HBM for the pairing buffers (~7 GB per 2^20 G1 points): keep the set usable without the pairing levels
       free_pair_ws(b);
       b->no_pair = 1;
       (void)hipGetLastError();
-      p = plan_for<C>(b, n);
+      p = plan_for<C>(b, n, knobs);
     }
-    if (int rc = ensure_ws<C>(b, n, p)) return rc;
+    if (int rc = ensure_ws<C>(b, n, p, knobs)) return rc;
     for (int i = 0; i < 5; ++i)
       if (!b->ev[i]) HIP_TRY(hipEventCreate(&b->ev[i]));
   }
@@ -339,13 +309,14 @@ constexpr uint32_t PAIR_MAX_LANES = 65536u, PAIR_MIN_B = 8u;
 // 0..4).  What a level costs besides its products is one inversion per lane (0.3 ms of wave time whatever the batch length), so
 // the floor on the batch length that round 2 used (48 additions per inversion) was the wrong economy for slices: it left most of
 // the machine idle behind a few lanes -- at 2^18 G1 points three levels take 8.8 ms with batches of 19..76 on every lane and
-// 9.4 ms with the floor, against 10.2 ms without levels.  MNT753_MSM_PAIR=<levels> overrides, 0 turns the pass off.
+// 9.4 ms with the floor, against 10.2 ms without levels.  MNT753_MSM_PAIR=<levels> overrides, 0 turns the pass off; a count forced
+// on the base set (mnt753_self_test) overrides both.
 template <class V>
-int pair_levels(uint64_t entries) {
+int pair_levels(uint64_t entries, const mnt753_bases* b, const MsmKnobs& knobs) {
   if constexpr (V::F::DEG != 1 && V::F::LANES == 1) return 0;   // (one-lane Fq2 / Fq3: not instantiated by the product)
   else {
-    if (g_force_pair_levels >= 0) return g_force_pair_levels;
-    if (const char* e = getenv("MNT753_MSM_PAIR")) { int v = atoi(e); return v < 0 ? 0 : (v > 6 ? 6 : v); }
+    if (b->force_pair_levels >= 0) return b->force_pair_levels;
+    if (knobs.pair >= 0) return knobs.pair;
     if constexpr (V::F::LANES == 1) {          // G1: 2^18 points and up (2^17: 5.3 ms plain, 5.5 with two levels)
       if (entries >= ((uint64_t)1 << 23)) return 3;
     } else if constexpr (V::F::LANES == 2) {   // two-lane Fq2: more arithmetic per gathered byte, crossover ~2^17 points
@@ -360,15 +331,16 @@ int pair_levels(uint64_t entries) {
   }
 }
 // Irregular levels behind the regular ones (k_pair_level<.., IRR>, msm_kernels.hip.h): MNT753_MSM_IRR=<levels> overrides, 0 turns
-// them off.  A level is worth its inversion (one per lane, ~0.3 ms of wave time whatever the batch) while it still has a batch per
-// lane, and worth anything only while buckets hold more than a couple of slots; from the one-GPU sweep of round 3
+// them off; a count forced on the base set overrides both.  A level is worth its inversion (one per lane, ~0.3 ms of wave time
+// whatever the batch) while it still has a batch per lane, and worth anything only while buckets hold more than a couple of slots;
+// from the one-GPU sweep of round 3
 // (profiles/r03/irregular_levels_sweep.txt): at least 16 output slots per lane for the base fields, 10 for the lane-split ones (their
 // additions cost three times as much against the same inversion), at most three levels.
 //   2^20 points:  G1 25.7 -> 25.2 ms with two levels, Fq2 G2 70.0 -> 66.5 ms with three;  3 * 2^20 G1 points (H | L | B1): 66.3 -> 62.8.
 template <class C>
-int irr_levels_for(uint64_t entries, int regular_levels, uint32_t n_buckets) {
-  if (g_force_irr_levels >= 0) return g_force_irr_levels;
-  if (const char* e = getenv("MNT753_MSM_IRR")) { int v = atoi(e); return v < 0 ? 0 : (v > 8 ? 8 : v); }
+int irr_levels_for(uint64_t entries, int regular_levels, uint32_t n_buckets, const mnt753_bases* b, const MsmKnobs& knobs) {
+  if (b->force_irr_levels >= 0) return b->force_irr_levels;
+  if (knobs.irr >= 0) return knobs.irr;
   const double lanes = (double)std::min<uint32_t>(machine_lanes(C::F::LANES), C::F::LANES == 3 ? PAIR_MAX_LANES / 3u : PAIR_MAX_LANES / (uint32_t)C::F::LANES);
   const double min_batch = C::F::LANES == 1 ? 16.0 : 10.0;
   double slots = (double)entries / (double)(1u << regular_levels) + 0.5 * n_buckets;
@@ -385,6 +357,14 @@ int irr_levels_for(uint64_t entries, int regular_levels, uint32_t n_buckets) {
 // level-1 slots of the worst case of plan p: (W n + n_buckets (2^L - 1)) / 2
 inline uint64_t pair_cap1(const MsmPlan& p, size_t n) {
   return ((uint64_t)p.W * n + (uint64_t)p.n_buckets * (((uint64_t)1 << p.pair_levels) - 1)) / 2;
+}
+// the device's pooled level buffers, bound to base set b
+inline void bind_pair_pool(mnt753_bases* b) {
+  const PairPool& pool = pair_pool_of(b);
+  b->d_pairpts[0] = static_cast<uint32_t*>(pool.buf[0]);
+  b->d_pairpts[1] = static_cast<uint32_t*>(pool.buf[1]);
+  b->d_sorted2 = static_cast<uint32_t*>(pool.buf[2]);
+  b->d_pair_ws = static_cast<uint32_t*>(pool.buf[3]);
 }
 // buffers of the pairing levels for an MSM over n points with plan p; grow only
 template <class V, class C>
@@ -417,18 +397,12 @@ int ensure_pair_ws(mnt753_bases* b, const MsmPlan& p, size_t n) {
           pool.cap[i] = need[i];
         }
       }
-      b->d_pairpts[0] = static_cast<uint32_t*>(pool.buf[0]);
-      b->d_pairpts[1] = static_cast<uint32_t*>(pool.buf[1]);
-      b->d_sorted2 = static_cast<uint32_t*>(pool.buf[2]);
-      b->d_pair_ws = static_cast<uint32_t*>(pool.buf[3]);
+      bind_pair_pool(b);
     }
     if (b->pair_cap >= cap1 && b->pair_buckets >= p.n_buckets) return 0;
     // the set's own small buffers
     free_pair_ws(b);
-    b->d_pairpts[0] = static_cast<uint32_t*>(pair_pool_of(b).buf[0]);
-    b->d_pairpts[1] = static_cast<uint32_t*>(pair_pool_of(b).buf[1]);
-    b->d_sorted2 = static_cast<uint32_t*>(pair_pool_of(b).buf[2]);
-    b->d_pair_ws = static_cast<uint32_t*>(pair_pool_of(b).buf[3]);
+    bind_pair_pool(b);
     HIP_TRY(hipMalloc(&b->d_fix, sizeof(uint32_t) * nbA));
     HIP_TRY(hipMalloc(&b->d_gen, sizeof(uint32_t) * aff_words<V>()));
     HIP_TRY(hipMalloc(&b->d_irr_offs[0], sizeof(uint32_t) * (nbA + 1)));
@@ -452,30 +426,11 @@ int ensure_pair_ws(mnt753_bases* b, const MsmPlan& p, size_t n) {
     return 0;
   }
 }
-// workspace for the configuration the point kernels of group C currently run with
-template <class C>
-int ensure_pair_ws_for(mnt753_bases* b, const MsmPlan& p, size_t n) {
-  using CS = typename SplitOf<C>::type;
-  if constexpr (!std::is_void<CS>::value) return ensure_pair_ws<CS, C>(b, p, n);
-  else return ensure_pair_ws<C, C>(b, p, n);
-}
-template <class C>
-int pair_levels_for(uint64_t entries) {
-  using CS = typename SplitOf<C>::type;
-  if constexpr (!std::is_void<CS>::value) return pair_levels<CS>(entries);
-  else return pair_levels<C>(entries);
-}
-template <class C>
-int irr_levels_for_group(uint64_t entries, int regular_levels, uint32_t n_buckets) {
-  using CS = typename SplitOf<C>::type;
-  if constexpr (!std::is_void<CS>::value) return irr_levels_for<CS>(entries, regular_levels, n_buckets);
-  else return irr_levels_for<C>(entries, regular_levels, n_buckets);
-}
 // plan of an MSM over n points of base set b: make_plan + the pairing levels this group / base set runs with
 template <class C>
-MsmPlan plan_for(const mnt753_bases* b, size_t n) {
-  MsmPlan p = make_plan(n, b->pre_c, point_lanes<C>());
-  p.pair_levels = b->no_pair ? 0 : pair_levels_for<C>((uint64_t)p.W * n);
+MsmPlan plan_for(const mnt753_bases* b, size_t n, const MsmKnobs& knobs) {
+  MsmPlan p = make_plan(n, b->pre_c, point_lanes<C>(), knobs);
+  p.pair_levels = b->no_pair ? 0 : pair_levels<PointCfg<C>>((uint64_t)p.W * n, b, knobs);
   // the padded list must keep 32-bit slot indices
   while (p.pair_levels > 0 && (uint64_t)p.W * n + (uint64_t)p.n_buckets * (((uint64_t)1 << p.pair_levels) - 1) >= 0xfffffff0ull) --p.pair_levels;
   // base fields: the first level keeps table offsets in 32-bit registers (uint4 units, 14 per row) -- a table of 64 GiB or more
@@ -483,8 +438,24 @@ MsmPlan plan_for(const mnt753_bases* b, size_t n) {
   if (point_lanes<C>() == 1 && C::F::DEG == 1 && (uint64_t)p.W * std::max<uint64_t>(b->n, n) * 14u >= 0xffffffffull) p.pair_levels = 0;
   // every field: blocked indices of level-1 slots (7 uint4 per element and lane) are 32-bit in the level kernels
   if (p.pair_levels > 0 && pair_cap1(p, n) * (uint64_t)point_lanes<C>() * 7u >= 0xffffff00ull) p.pair_levels = 0;
-  p.irr_levels = p.pair_levels > 0 ? irr_levels_for_group<C>((uint64_t)p.W * n, p.pair_levels, p.n_buckets) : 0;
+  p.irr_levels = p.pair_levels > 0 ? irr_levels_for<PointCfg<C>>((uint64_t)p.W * n, p.pair_levels, p.n_buckets, b, knobs) : 0;
   return p;
+}
+// One batched-affine level, k_pair_level<V, FIRST, LAST, IRR>: its rows go to `out`, its bucket offsets are `offs`.  The level kernels
+// stage their operands in 145 KB of dynamic LDS per workgroup: opt in once per kernel and DEVICE.
+template <class V, bool FIRST, bool LAST, bool IRR>
+int launch_pair_level(mnt753_bases* b, hipStream_t st, uint32_t lanes, const uint32_t* d_aff, const uint4* src_planes, size_t src_stride,
+                      const uint32_t* offs, uint32_t n_buckets, uint32_t shift, uint32_t* out, size_t out_stride, const uint32_t* irr_src) {
+  static std::atomic<uint32_t> lds_set{0};
+  const uint32_t dev_bit = 1u << (b->device & 31);
+  if (!(lds_set.load(std::memory_order_acquire) & dev_bit)) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_level<V, FIRST, LAST, IRR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PAIR_LDS_BYTES));
+    lds_set.fetch_or(dev_bit, std::memory_order_release);
+  }
+  hipLaunchKernelGGL((k_pair_level<V, FIRST, LAST, IRR>), dim3(blocks_for<typename V::F>(lanes)), dim3(256), PAIR_LDS_BYTES, st, d_aff, b->d_sorted, src_planes,
+                     src_stride, offs, n_buckets, shift, out, b->d_sorted2, reinterpret_cast<uint4*>(out), out_stride,
+                     reinterpret_cast<uint4*>(b->d_pair_ws), PAIR_MIN_B, lanes, b->d_gen, b->d_fix, irr_src);
+  return 0;
 }
 template <class V, class C>
 int pair_and_accumulate(const MsmPlan& p, size_t n, hipStream_t st, const uint32_t* d_aff, mnt753_bases* b, uint32_t* acc_lanes, uint32_t* acc_T, const uint32_t** acc_offs) {
@@ -520,24 +491,9 @@ int pair_and_accumulate(const MsmPlan& p, size_t n, hipStream_t st, const uint32
       const int first = l == 1, last = l == levels && irr == 0;
       // planes of a level that feeds another one: (x | y) x (even | odd slot), each holding cap / 2 slots, blocked
       const size_t out_stride = blk_quads((cap / 2 + 1) * (uint64_t)V::F::LANES + 64);
-#define MNT753_PAIR_LAUNCH(FST, LST)                                                                                                         \
-  do {                                                                                                                                      \
-    /* the level kernels stage their operands in 145 KB of dynamic LDS per workgroup: opt in once per kernel and DEVICE */                  \
-    static std::atomic<uint32_t> lds_set{0};                                                                                                \
-    const uint32_t dev_bit = 1u << (b->device & 31);                                                                                        \
-    if (!(lds_set.load(std::memory_order_acquire) & dev_bit)) {                                                                             \
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_level<V, FST, LST>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PAIR_LDS_BYTES)); \
-      lds_set.fetch_or(dev_bit, std::memory_order_release);                                                                                 \
-    }                                                                                                                                       \
-    hipLaunchKernelGGL((k_pair_level<V, FST, LST>), dim3(blocks_for<typename V::F>(lanes)), dim3(256), PAIR_LDS_BYTES, st, d_aff, b->d_sorted, src_planes, \
-                       src_stride, b->d_offsets, p.n_buckets, (uint32_t)(levels - l), out, b->d_sorted2, reinterpret_cast<uint4*>(out), out_stride,  \
-                       reinterpret_cast<uint4*>(b->d_pair_ws), min_B, lanes, b->d_gen, b->d_fix);                              \
-  } while (0)
-      if (first && last) MNT753_PAIR_LAUNCH(true, true);
-      else if (first) MNT753_PAIR_LAUNCH(true, false);
-      else if (last) MNT753_PAIR_LAUNCH(false, true);
-      else MNT753_PAIR_LAUNCH(false, false);
-#undef MNT753_PAIR_LAUNCH
+      const auto level = first ? (last ? launch_pair_level<V, true, true, false> : launch_pair_level<V, true, false, false>)
+                               : (last ? launch_pair_level<V, false, true, false> : launch_pair_level<V, false, false, false>);
+      if (int rc = level(b, st, lanes, d_aff, src_planes, src_stride, b->d_offsets, p.n_buckets, (uint32_t)(levels - l), out, out_stride, nullptr)) return rc;
 #ifdef MNT753_PAIR_TIMING
       {
         unsigned long long h[8], z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -569,20 +525,8 @@ int pair_and_accumulate(const MsmPlan& p, size_t n, hipStream_t st, const uint32
       const uint32_t lanes = (uint32_t)std::min<uint64_t>(max_lanes, (cap + min_B - 1) / min_B);
       uint32_t* out = b->d_pairpts[(l - 1) & 1];
       const size_t out_stride = blk_quads((cap / 2 + 1) * (uint64_t)V::F::LANES + 64);
-#define MNT753_IRR_LAUNCH(LST)                                                                                                               \
-  do {                                                                                                                                      \
-    static std::atomic<uint32_t> lds_set{0};                                                                                                \
-    const uint32_t dev_bit = 1u << (b->device & 31);                                                                                        \
-    if (!(lds_set.load(std::memory_order_acquire) & dev_bit)) {                                                                             \
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_level<V, false, LST, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PAIR_LDS_BYTES)); \
-      lds_set.fetch_or(dev_bit, std::memory_order_release);                                                                                 \
-    }                                                                                                                                       \
-    hipLaunchKernelGGL((k_pair_level<V, false, LST, true>), dim3(blocks_for<typename V::F>(lanes)), dim3(256), PAIR_LDS_BYTES, st, d_aff, b->d_sorted, src_planes, \
-                       src_stride, offs_out, p.n_buckets, 0u, out, b->d_sorted2, reinterpret_cast<uint4*>(out), out_stride,                  \
-                       reinterpret_cast<uint4*>(b->d_pair_ws), min_B, lanes, b->d_gen, b->d_fix, b->d_irr_src);                              \
-  } while (0)
-      if (k == irr) MNT753_IRR_LAUNCH(true); else MNT753_IRR_LAUNCH(false);
-#undef MNT753_IRR_LAUNCH
+      const auto level = k == irr ? launch_pair_level<V, false, true, true> : launch_pair_level<V, false, false, true>;
+      if (int rc = level(b, st, lanes, d_aff, src_planes, src_stride, offs_out, p.n_buckets, 0u, out, out_stride, b->d_irr_src)) return rc;
       src_planes = reinterpret_cast<const uint4*>(out);
       src_stride = out_stride;
       last_rows = out;
@@ -610,13 +554,11 @@ int pair_and_accumulate(const MsmPlan& p, size_t n, hipStream_t st, const uint32
 // The stages that run point arithmetic.  V = the configuration the point-operation VM is instantiated with (C itself,
 // or its lane-split counterpart); kernels that only move points are layout-agnostic and use C.
 template <class V, class C>
-int point_stages(const MsmPlan& p, size_t n, hipStream_t st, const uint32_t* d_aff, mnt753_bases* b, uint32_t** result) {
+int point_stages(const MsmPlan& p, size_t n, hipStream_t st, const uint32_t* d_aff, mnt753_bases* b, const MsmKnobs& knobs, uint32_t** result) {
   const int n_pair_levels = p.pair_levels;
   uint32_t acc_lanes = p.n_lanes;   // lanes the accumulate kernel ran with (= edge slots / 2)
   uint32_t acc_T = p.T;             // entries per lane it was given, and the bucket offsets it walked (the last level's, behind pairing levels)
   const uint32_t* acc_offs = b->d_offsets;
-  g_last_pair_levels = n_pair_levels;
-  g_last_irr_levels = n_pair_levels > 0 ? p.irr_levels : 0;
   if (n_pair_levels > 0) {
     if (int rc = pair_and_accumulate<V, C>(p, n, st, d_aff, b, &acc_lanes, &acc_T, &acc_offs)) return rc;
   } else {
@@ -640,7 +582,7 @@ int point_stages(const MsmPlan& p, size_t n, hipStream_t st, const uint32_t* d_a
     // it) spreads each addition over a group of lanes, the levels before it run one VM addition per lane over the list.
     // MNT753_EDGE_FLOW_NODES moves the boundary: the tests use it to run EVERY level of deep trees through either form (the inlined VM
     // addition of round 4's first tree kernel was miscompiled exactly there).
-    const uint64_t EDGE_FLOW_NODES = getenv("MNT753_EDGE_FLOW_NODES") ? strtoull(getenv("MNT753_EDGE_FLOW_NODES"), nullptr, 10)
+    const uint64_t EDGE_FLOW_NODES = knobs.edge_flow_set ? knobs.edge_flow_nodes
                                      : (C::F::DEG == 1 ? 32768 : (Flow<C>::K3 ? 8192 : 16384));   // (K3: two additions per wave, 2048 per round)
     uint32_t* counts = b->d_edge_flags + 40;               // nodes of level l, behind the 40 flags
     uint4* lists[2] = {reinterpret_cast<uint4*>(b->d_edge_tmp), reinterpret_cast<uint4*>(b->d_edge_tmp) + acc_lanes};
@@ -712,16 +654,21 @@ int msm_start_t(mnt753_bases* b, size_t base_offset, const uint64_t* scalars, in
   if (b->pending) return set_error(MNT753_EINVAL, "msm_start: this base set already has an MSM in flight (finish it first)");
   b->pending = 1; b->pending_n = n; b->pending_stream = st;
   if (n == 0) return 0;
-  MsmPlan p = plan_for<C>(b, n);
-  if (p.pair_levels > 0 && ensure_pair_ws_for<C>(b, p, n) != 0) {
+  const MsmKnobs knobs = msm_knobs();
+  MsmPlan p = plan_for<C>(b, n, knobs);
+  if (p.pair_levels > 0 && ensure_pair_ws<PointCfg<C>, C>(b, p, n) != 0) {
     // the pairing buffers do not fit (a larger MSM than the set was created for, on a full device): plain accumulate
     free_pair_ws(b);
     b->no_pair = 1;
     (void)hipGetLastError();
-    p = plan_for<C>(b, n);
+    p = plan_for<C>(b, n, knobs);
   }
-  if (int rc = ensure_ws<C>(b, n, p)) return rc;
-  g_last_plan[0] = p.c; g_last_plan[1] = p.W; g_last_plan[2] = p.pre; g_last_plan[3] = (int)p.T;
+  if (int rc = ensure_ws<C>(b, n, p, knobs)) return rc;
+  // the plan is final: the record of the last run (the irregular levels the plan asks for, also where pair_and_accumulate has room for fewer)
+  b->run_plan = p;
+  g_last_run.plan[0] = p.c; g_last_run.plan[1] = p.W; g_last_run.plan[2] = p.pre; g_last_run.plan[3] = (int)p.T;
+  g_last_run.pair_levels = p.pair_levels;
+  g_last_run.irr_levels = p.pair_levels > 0 ? p.irr_levels : 0;
   for (int i = 0; i < 5; ++i)
     if (!b->ev[i]) HIP_TRY(hipEventCreate(&b->ev[i]));
   const uint32_t* d_scal;
@@ -735,9 +682,9 @@ int msm_start_t(mnt753_bases* b, size_t base_offset, const uint64_t* scalars, in
   const uint32_t* d_aff = p.pre ? b->d_aff : b->d_aff + base_offset * aff_words<C>();
   const uint8_t* d_inf = b->d_inf + base_offset;
   HIP_TRY(hipEventRecord(b->ev[0], st));
-  if (b->d_part_ws && sort_mode((uint64_t)p.W * n) == SORT_PART && msm_sort_partition_fits(p.n_buckets, p.W)) {
-    if (int rc = msm_sort_partition(C::FR, d_scal, d_inf, n, p, p.pre ? (uint32_t)b->n : 0u, p.pre ? (uint32_t)base_offset : 0u, b->d_keys_out, b->d_vals_out,
-                                    b->d_part_ws, b->d_hist, b->d_offsets, b->d_cursor, b->d_blocksums, b->d_total, b->d_sorted, st))
+  if (b->d_part_ws && sort_mode((uint64_t)p.W * n, knobs) == SORT_PART && msm_sort_partition_fits(p.n_buckets, p.W)) {
+    if (int rc = msm_sort_partition(C::FR, d_scal, d_inf, n, p, p.pre ? (uint32_t)b->n : 0u, p.pre ? (uint32_t)base_offset : 0u, knobs.sort_generic, b->d_keys_out,
+                                    b->d_vals_out, b->d_part_ws, b->d_hist, b->d_offsets, b->d_cursor, b->d_blocksums, b->d_total, b->d_sorted, st))
       return rc;
   } else {
     HIP_TRY(hipMemsetAsync(b->d_hist, 0, sizeof(uint32_t) * (size_t)p.n_buckets, st));
@@ -762,13 +709,7 @@ int msm_start_t(mnt753_bases* b, size_t base_offset, const uint64_t* scalars, in
   // point stages: with the lane-split configuration of the group (Fq2: two lanes per point, Fq3: three) when it has
   // one, otherwise one lane per point
   uint32_t* cur = nullptr;
-  {
-    int rc;
-    using CS = typename SplitOf<C>::type;
-    if constexpr (!std::is_void<CS>::value) rc = point_stages<CS, C>(p, n, st, d_aff, b, &cur);
-    else rc = point_stages<C, C>(p, n, st, d_aff, b, &cur);
-    if (rc) return rc;
-  }
+  if (int rc = point_stages<PointCfg<C>, C>(p, n, st, d_aff, b, knobs, &cur)) return rc;
   const uint32_t NS = p.n_sets, NP = NS * (uint32_t)p.c;   // c points per bucket set: T, G_0 .. G_{c-2}
   hipLaunchKernelGGL((k_points_to_wire<C>), dim3((NP + 63) / 64), dim3(64), 0, st, cur, b->d_wire_out, NP);
   HIP_TRY(hipGetLastError());
@@ -791,12 +732,13 @@ int msm_finish_t(mnt753_bases* b, uint64_t* out) {
   auto t0 = std::chrono::steady_clock::now();
   horner_host<HC>(b->h_wire_out, b->pending_sets, b->pending_c, out);   // one point with the window table: a copy
   auto t1 = std::chrono::steady_clock::now();
+  float* t = g_last_run.timing;
   float ms;
-  HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1])); g_last_timing[1] = ms;
-  HIP_TRY(hipEventElapsedTime(&ms, b->ev[1], b->ev[2])); g_last_timing[2] = ms;
-  HIP_TRY(hipEventElapsedTime(&ms, b->ev[2], b->ev[3])); g_last_timing[3] = ms;
-  g_last_timing[4] = std::chrono::duration<float, std::milli>(t1 - t0).count();
-  HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[3])); g_last_timing[0] = ms + g_last_timing[4];
+  HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1])); t[1] = ms;
+  HIP_TRY(hipEventElapsedTime(&ms, b->ev[1], b->ev[2])); t[2] = ms;
+  HIP_TRY(hipEventElapsedTime(&ms, b->ev[2], b->ev[3])); t[3] = ms;
+  t[4] = std::chrono::duration<float, std::milli>(t1 - t0).count();
+  HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[3])); t[0] = ms + t[4];
   return 0;
 }
 

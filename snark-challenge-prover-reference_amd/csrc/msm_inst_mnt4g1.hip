@@ -3,7 +3,9 @@
 #include "msm_api.hpp"
 namespace mnt753 {
 void msm_free_workspace(mnt753_bases* b) { free_ws(b); }
-int bases_create_mnt4g1(mnt753_bases* b, const uint64_t* affine, int on_device, size_t n) { return bases_create_t<Mnt4G1>(b, affine, on_device, n); }
+int bases_create_mnt4g1(mnt753_bases* b, const uint64_t* affine, int on_device, size_t n, const MsmKnobs& knobs) {
+  return bases_create_t<Mnt4G1>(b, affine, on_device, n, knobs);
+}
 int msm_mnt4g1(mnt753_bases* b, size_t base_offset, const uint64_t* scalars, int scalars_on_device, size_t n, uint64_t* out, hipStream_t st) {
   return msm_t<Mnt4G1, host::HMnt4G1>(b, base_offset, scalars, scalars_on_device, n, out, st);
 }

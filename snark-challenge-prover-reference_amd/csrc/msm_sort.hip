@@ -10,8 +10,6 @@
 // The order of the entries inside a bucket is whatever the passes produce; the MSM result is a sum and does not depend on it.
 // Group-independent, hence its own translation unit.
 #include <hip/hip_runtime.h>
-#include <cstdlib>
-#include <cstring>
 
 #include "common_host.hpp"
 #include "msm_kernels.hip.h"
@@ -409,7 +407,7 @@ __global__ void __launch_bounds__(256) k_bucket_pad(const uint32_t* __restrict__
 namespace mnt753 {
 // part_ws: 3 * (PART_MAX + 1) u32 (totals, starts, cursors)
 int msm_sort_partition(int frm, const uint32_t* d_scal, const uint8_t* d_inf, size_t n, const MsmPlan& p, uint32_t entry_stride, uint32_t entry_base,
-                       uint32_t* keys_out, uint32_t* vals_out, uint32_t* part_ws, uint32_t* d_hist, uint32_t* d_offsets, uint32_t* d_cursor,
+                       bool generic_only, uint32_t* keys_out, uint32_t* vals_out, uint32_t* part_ws, uint32_t* d_hist, uint32_t* d_offsets, uint32_t* d_cursor,
                        uint32_t* d_blocksums, uint32_t* d_total, uint32_t* d_sorted, hipStream_t st) {
   const size_t total = (size_t)p.W * n;
   const uint32_t n_parts = (p.n_buckets + PART_BUCKETS - 1u) >> PART_BITS;
@@ -421,9 +419,7 @@ int msm_sort_partition(int frm, const uint32_t* d_scal, const uint8_t* d_inf, si
   HIP_TRY(hipMemsetAsync(part_total, 0, sizeof(uint32_t) * (PART_MAX + 1), st));
   HIP_TRY(hipMemsetAsync(d_hist, 0, sizeof(uint32_t) * (size_t)p.n_buckets, st));
   // window width known to a template (14 .. 22: every width pick_precomp_bits / pick_window_bits hands out for sets this large):
-  // digits from registers, one staged word per entry (k_part_pass_c); any other width, or MNT753_MSM_SORT=generic: k_part_pass
-  const char* sort_env = getenv("MNT753_MSM_SORT");
-  const bool generic_only = sort_env && !strcmp(sort_env, "generic");
+  // digits from registers, one staged word per entry (k_part_pass_c); any other width, or generic_only (MNT753_MSM_SORT=generic): k_part_pass
   const bool by_width = !generic_only && p.c >= 14 && p.c <= 22 && part_place_lds_c(n_parts, p.W) <= PART_LDS_LIMIT;
   if (by_width) {
     const size_t lds_place = part_place_lds_c(n_parts, p.W), lds_count = sizeof(uint32_t) * (size_t)n_parts;

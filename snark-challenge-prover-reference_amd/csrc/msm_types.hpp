@@ -46,6 +46,8 @@ struct mnt753_bases {
   size_t pair_buckets = 0;   // buckets d_fix holds
   size_t sorted_cap = 0;     // entries d_sorted holds (padded layout: W*n + n_buckets*(2^levels - 1))
   int no_pair = 0;       // the pairing workspace could not be allocated: this set runs the plain accumulate
+  int force_pair_levels = -1, force_irr_levels = -1;   // >= 0: level counts for this set's MSMs (mnt753_self_test), ahead of MNT753_MSM_PAIR / _IRR
+  mnt753::MsmPlan run_plan{};   // plan of the last MSM started on this set
   int registered = 0;    // counted in its device's PairPool (mnt753_bases_create got as far as registering the set)
   uint32_t* d_wire_out = nullptr;
   uint64_t* h_wire_out = nullptr;   // pinned
@@ -74,6 +76,13 @@ struct PairPool {
   bool used = false;
   int refs = 0;                    // base sets alive on the device
 };
+// diagnostics of the last MSM in the process (mnt753_msm_last_timing / _plan / _pair_levels / _irr_levels)
+struct MsmLastRun {
+  float timing[5] = {0, 0, 0, 0, 0};   // total, sort, accumulate, reduction, host tail (ms)
+  int plan[4] = {0, 0, 0, 0};          // c, W, pre, T
+  int pair_levels = 0, irr_levels = 0;
+};
+extern MsmLastRun g_last_run;
 constexpr int PAIR_POOL_DEVICES = 32;
 extern PairPool g_pair_pool[PAIR_POOL_DEVICES];
 inline PairPool& pair_pool_of(const mnt753_bases* b) { return g_pair_pool[(unsigned)b->device % PAIR_POOL_DEVICES]; }
