@@ -32,6 +32,15 @@ int mnt753_test_field_op(int mod, int op, const uint64_t* a, const uint64_t* b, 
  * fused multi-product multipliers, ds_bpermute exchange).
  * op: 0 a*b, 1 a*a, 2 a^-1, 3 a+b, 4 a-b, 5 -a, 6 (a == b) as the element 1 or 0 (the zero test the kernels branch on). */
 int mnt753_test_ext_op(int curve, int split, int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);
+/* The device field primitives on RAW limbs (csrc/field_raw_ops.hip.h), n records, host pointers: in holds 6 operands x 27 uint32
+ * limbs per record exactly as a kernel holds them (no wire conversion: lazy ranges, un-normalised and signed limbs), out 2 x 27 limbs
+ * plus one flag word per record.  k: the scalar argument of the op (fp_mul_small's multiplier, fp_addsub_raw's sign, the selector of
+ * the NTT composite).  op: the FieldRawOp codes of field_raw_ops.hip.h.  The caller keeps every operand inside the contract stated
+ * above the primitive in fp753.hip.h / fp_inv.hip.h. */
+int mnt753_test_field_raw(int mod, int op, const uint32_t* in, size_t n, uint32_t k, uint32_t* out);
+/* mnt753_test_ext_op on RAW components: 27 device limbs per component (c0 | c1 [| c2]) in and out, no wire conversion.
+ * op: 0 a*b, 1 a*a, 2 a^-1, 3 is_zero(a) as 0 / 1 in limb 0 of component 0 (every other word 0). */
+int mnt753_test_ext_raw(int curve, int split, int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out);
 /* Every form of the group law the MSM kernels contain, on n pairs of points.  p_proj / q_proj / out_proj: projective X | Y | Z in
  * wire form (any representative; Z == 0 is the identity), host pointers.  group: MNT753_G1 / MNT753_G2; split (G2 only): 0 = one
  * lane per point, 1 = the lane-split configuration.  Reference: operator+ / mixed_add / dbl of mnt4753_G1 (depends/libff/libff/

@@ -122,13 +122,15 @@ def test_lib():
     if not os.path.exists(path):
         raise Mnt753Error(f"{path} not found: build the HIP extension first (make, or __graft_entry__.build())")
     L = C.CDLL(path)
-    u64p, sz, i = C.POINTER(C.c_uint64), C.c_size_t, C.c_int
+    u64p, u32p, sz, i = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_size_t, C.c_int
     sig = {
         "mnt753_synth_points": (i, [i, i, C.c_uint64, sz, u64p, i]),
         "mnt753_synth_expected_msm": (i, [i, i, C.c_uint64, sz, u64p, u64p]),
         "mnt753_test_field_op": (i, [i, i, u64p, u64p, sz, u64p]),
         "mnt753_test_ext_op": (i, [i, i, i, u64p, u64p, sz, u64p]),
         "mnt753_test_point_op": (i, [i, i, i, i, u64p, u64p, sz, u64p]),
+        "mnt753_test_field_raw": (i, [i, i, u32p, sz, C.c_uint32, u32p]),
+        "mnt753_test_ext_raw": (i, [i, i, i, u32p, u32p, sz, u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -458,6 +460,31 @@ def test_field_op(mod, op, a, b=None):
     return out
 
 
+FIELD_RAW_IN_WORDS, FIELD_RAW_OUT_WORDS = 6 * 27, 2 * 27 + 1
+
+
+def test_field_raw(mod, op, records, k=0):
+    """Test hook: one device field primitive on raw limbs (csrc/field_raw_ops.hip.h).  records: uint32 array of shape (n, 162)
+    (6 operands x 27 limbs); returns (n, 55): two results of 27 limbs and a flag word."""
+    rec = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, FIELD_RAW_IN_WORDS)
+    out = np.zeros((rec.shape[0], FIELD_RAW_OUT_WORDS), dtype=np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    _check(test_lib().mnt753_test_field_raw(mod, op, rec.ctypes.data_as(u32p), rec.shape[0], k, out.ctypes.data_as(u32p)), "mnt753_test_field_raw")
+    return out
+
+
+def test_ext_raw(curve, split, op, a, b=None):
+    """Test hook: Fq2 (MNT4753) / Fq3 (MNT6753) on raw device components; a, b: uint32 arrays of shape (n, deg * 27)."""
+    deg = 2 if curve == 0 else 3
+    a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, deg * 27)
+    b = a if b is None else np.ascontiguousarray(b, dtype=np.uint32).reshape(-1, deg * 27)
+    out = np.zeros_like(a)
+    u32p = C.POINTER(C.c_uint32)
+    _check(test_lib().mnt753_test_ext_raw(curve, int(split), op, a.ctypes.data_as(u32p), b.ctypes.data_as(u32p), a.shape[0],
+                                          out.ctypes.data_as(u32p)), "mnt753_test_ext_raw")
+    return out
+
+
 def test_ext_op(curve, split, op, a, b=None):
     """Test hook: Fq2 (MNT4753) / Fq3 (MNT6753) on the device, element-wise; split = the lane-split form of the G2 kernels."""
     a, pa = _u64(a)
@@ -478,6 +505,8 @@ def test_point_op(curve, group, split, op, p, q=None):
     return out
 
 
+test_field_raw.__test__ = False
+test_ext_raw.__test__ = False
 test_ext_op.__test__ = False
 test_point_op.__test__ = False
 

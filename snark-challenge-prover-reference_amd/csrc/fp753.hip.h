@@ -260,10 +260,15 @@ HD void fp_half(Fp<M>& r, const Fp<M>& a) {
 // addition needs seven of them.  The 28-bit limbs leave four spare bits per word, so differences are taken LIMB-WISE with no
 // carry at all (27 instructions; limbs become signed, |limb| < 2^29 after one addition / subtraction of 28-bit operands) and fed
 // straight into a multiplier whose product half uses the signed multiply-add (v_mad_i64_i32, same rate as v_mad_u64_u32):
-//   * fp_mul_s / fp_sqr_s: operands with int32 limbs, 27 |a_i| |b_j| + 27 2^56 < 2^63 (e.g. 2^29 x 2^28 or 2^30 x 2^28); the
+//   * fp_mul_s / fp_sqr_s: operands with int32 limbs, 27 |a_i| |b_j| + (2^28 - 1) sum_j p_j + 2^36 < 2^63 per column (the reduction's
+//     products m_i p_j add up to at most (2^28 - 1) sum_j p_j < 14.4 2^56 for both moduli, the carry in stays below 2^36): |a_i| |b_j|
+//     < 4.2 2^56, e.g. 2^29 x 2^29 or 2^30 x 2^28 (fp_sqr_s: |a_i| < 2^29 against 2a, half as many cross terms); the
 //     Montgomery reduction is unchanged (m_k from the low 28 bits of the two's-complement column, arithmetic shifts).  Result:
 //     limbs 0..25 in [0, 2^28), limb 26 SIGNED, value in (-|a b| / R', |a b| / R' + p).
-//   * fp_norm: signed un-normalised limbs (|limb| < 2^30, |value| < 5p) -> limbs in [0, 2^28), value in [0.49p, 1.51p), a subset
+//   * fp_norm: signed un-normalised limbs (|value| < 5p, |limb| < 2^30 and |limb| + 2^28 |q| < 2^31 - 2^4 for the multiple q of p it
+//     takes off, q = floor(value / p - 1/2) or one off within 2^-20 p of a half-integer multiple of p: |q| <= 6, and |limb| < 2^29
+//     always qualifies for |q| <= 5, |limb| < 2^30 for |q| <= 3 -- beyond that a limb's int32 sum wraps and the carry is lost)
+//     -> limbs in [0, 2^28), value in [0.49p, 1.51p), a subset
 //     of the lazy range [0, 2p) of everything else in this file: the quotient comes from the top limb alone (the lower limbs
 //     move it by < 2^-20 p), one pass subtracts q p and carries -- 4 instructions per limb, and only the two coordinates an
 //     addition hands on need it.
@@ -446,7 +451,7 @@ HD void fp_addsub_raw(Fp<M>& r, const Fp<M>& a, const Fp<M>& y, bool subtract) {
 #pragma unroll
   for (int i = 0; i < NL; ++i) r.l[i] = a.l[i] + (y.l[i] ^ mk) + one;
 }
-// signed un-normalised limbs (|limb| < 2^30 - 2^28 |q|... see above: |value| < 5p) -> [0.49p, 1.51p), limbs in [0, 2^28)
+// signed un-normalised limbs (|value| < 5p, |limb| + 2^28 |q| < 2^31 - 2^4: see above) -> [0.49p, 1.51p), limbs in [0, 2^28)
 template <int M>
 HD void fp_norm(Fp<M>& r, const Fp<M>& a) {
   const float t = (float)(int32_t)a.l[NL - 1] * (1.0f / (float)FPC[M].p[NL - 1]) - 0.5f;

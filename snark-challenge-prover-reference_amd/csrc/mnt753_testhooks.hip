@@ -12,6 +12,7 @@
 #include "common_host.hpp"
 #include "../../include/mnt753_hip_test.h"
 #include "msm_kernels.hip.h"
+#include "field_raw_ops.hip.h"
 
 using namespace mnt753;
 
@@ -71,6 +72,37 @@ extern "C" int mnt753_test_field_op(int mod, int op, const uint64_t* a, const ui
   return 0;
 }
 
+// ---- the field primitives on raw limbs (field_raw_ops.hip.h), one record per thread -------------------------------------------
+namespace {
+struct DevBuf {   // freed on every path out of a hook
+  uint32_t* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+template <int M>
+__global__ void __launch_bounds__(64) k_field_raw(int op, const uint32_t* __restrict__ in, uint32_t k, uint32_t* __restrict__ out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  field_raw_op<M>(op, in + FR_IN_WORDS * i, k, out + FR_OUT_WORDS * i);
+}
+}  // namespace
+
+extern "C" int mnt753_test_field_raw(int mod, int op, const uint32_t* in, size_t n, uint32_t k, uint32_t* out) {
+  if (mod < 0 || mod > 1 || op < 0 || op >= FR_NUM_OPS || (n && (!in || !out)) || n > 0x7fffffffu)
+    return set_error(MNT753_EINVAL, "test_field_raw: bad argument");
+  if (int rc = require_device()) return rc;
+  if (n == 0) return 0;
+  DevBuf din, dout;
+  HIP_TRY(hipMalloc(&din.p, sizeof(uint32_t) * FR_IN_WORDS * n));
+  HIP_TRY(hipMalloc(&dout.p, sizeof(uint32_t) * FR_OUT_WORDS * n));
+  HIP_TRY(hipMemcpy(din.p, in, sizeof(uint32_t) * FR_IN_WORDS * n, hipMemcpyHostToDevice));
+  const unsigned g = (unsigned)((n + 63) / 64);
+  if (mod == MOD_A) hipLaunchKernelGGL((k_field_raw<MOD_A>), dim3(g), dim3(64), 0, 0, op, din.p, k, dout.p, n);
+  else hipLaunchKernelGGL((k_field_raw<MOD_B>), dim3(g), dim3(64), 0, 0, op, din.p, k, dout.p, n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout.p, sizeof(uint32_t) * FR_OUT_WORDS * n, hipMemcpyDeviceToHost));
+  return 0;
+}
 
 // ---- extension-field elements, element-wise ------------------------------------------------------------------------------
 namespace {
@@ -131,10 +163,49 @@ __global__ void __launch_bounds__(256, 1) k_ext_op(int op, const uint32_t* __res
   if (t < n) ext_store<F>(out_wire + (size_t)i * EWW, r);
 }
 
-struct DevBuf {   // freed on every path out of a hook
-  uint32_t* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
+// The same on raw components: NL device limbs per component (c0 | c1 [| c2]), loaded and returned exactly as the kernels hold them.
+// op: 0 a*b, 1 a*a, 2 a^-1, 3 is_zero(a) as 0 / 1 in limb 0 of component 0 (every other word 0)
+template <class F>
+__global__ void __launch_bounds__(256, 1) k_ext_raw(int op, const uint32_t* __restrict__ a_raw, const uint32_t* __restrict__ b_raw,
+                                                   uint32_t* __restrict__ out_raw, uint32_t n) {
+  using E = typename F::E;
+  const uint32_t t = logical_lane<F>();
+  const uint32_t i = t < n ? t : n - 1u;
+  constexpr int EW = NL * F::DEG;    // words of one element
+  E a, b, r;
+  auto load = [&](E& x, const uint32_t* p) {
+    if constexpr (F::LANES == 1) {
+      for (int c = 0; c < F::DEG; ++c)
+        for (int j = 0; j < NL; ++j) F::comp(x, c).l[j] = p[c * NL + j];
+    } else {
+      for (int j = 0; j < NL; ++j) x.l[j] = p[lane_comp<F>() * NL + j];
+    }
+  };
+  load(a, a_raw + (size_t)i * EW);
+  load(b, b_raw + (size_t)i * EW);
+  switch (op) {
+    case 0: F::mul(r, a, b); break;
+    case 1: F::mul(r, a, a); break;
+    case 2:
+      if constexpr (has_inv<F>::value) F::inv(r, a); else e_inv(r, a, (F*)nullptr);
+      break;
+    default: {
+      const bool z = F::is_zero(a);
+      F::zero(r);
+      if constexpr (F::LANES == 1) F::comp(r, 0).l[0] = z ? 1u : 0u;
+      else if (lane_comp<F>() == 0) r.l[0] = z ? 1u : 0u;
+    } break;
+  }
+  if (t >= n) return;
+  uint32_t* o = out_raw + (size_t)i * EW;
+  if constexpr (F::LANES == 1) {
+    for (int c = 0; c < F::DEG; ++c)
+      for (int j = 0; j < NL; ++j) o[c * NL + j] = F::comp(r, c).l[j];
+  } else {
+    for (int j = 0; j < NL; ++j) o[lane_comp<F>() * NL + j] = r.l[j];
+  }
+}
+
 template <class F>
 int run_ext_op(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
   const size_t bytes = 96 * (size_t)F::DEG * n;
@@ -143,6 +214,19 @@ int run_ext_op(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t*
   HIP_TRY(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice));
   hipLaunchKernelGGL((k_ext_op<F>), dim3(blocks_for<F>(n)), dim3(256), 0, 0, op, da.p, db.p, dout.p, (uint32_t)n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+template <class F>
+int run_ext_raw(int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out) {
+  const size_t bytes = sizeof(uint32_t) * NL * (size_t)F::DEG * n;
+  DevBuf da, db, dout;
+  HIP_TRY(hipMalloc(&da.p, bytes)); HIP_TRY(hipMalloc(&db.p, bytes)); HIP_TRY(hipMalloc(&dout.p, bytes));
+  HIP_TRY(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL((k_ext_raw<F>), dim3(blocks_for<F>(n)), dim3(256), 0, 0, op, da.p, db.p, dout.p, (uint32_t)n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
   return 0;
@@ -295,6 +379,14 @@ extern "C" int mnt753_test_ext_op(int curve, int split, int op, const uint64_t* 
   if (n == 0) return 0;
   if (curve == MNT753_CURVE_MNT4753) return split ? run_ext_op<Mnt4G2S::F>(op, a, b, n, out) : run_ext_op<Mnt4G2::F>(op, a, b, n, out);
   return split ? run_ext_op<Mnt6G2S::F>(op, a, b, n, out) : run_ext_op<Mnt6G2::F>(op, a, b, n, out);
+}
+
+extern "C" int mnt753_test_ext_raw(int curve, int split, int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out) {
+  if (curve < 0 || curve > 1 || op < 0 || op > 3 || (n && (!a || !b || !out)) || n > 0x7fffffffu) return set_error(MNT753_EINVAL, "test_ext_raw: bad argument");
+  if (int rc = require_device()) return rc;
+  if (n == 0) return 0;
+  if (curve == MNT753_CURVE_MNT4753) return split ? run_ext_raw<Mnt4G2S::F>(op, a, b, n, out) : run_ext_raw<Mnt4G2::F>(op, a, b, n, out);
+  return split ? run_ext_raw<Mnt6G2S::F>(op, a, b, n, out) : run_ext_raw<Mnt6G2::F>(op, a, b, n, out);
 }
 
 extern "C" int mnt753_test_point_op(int curve, int group, int split, int op, const uint64_t* p_proj, const uint64_t* q_proj, size_t n, uint64_t* out_proj) {

@@ -111,10 +111,14 @@ __global__ void __launch_bounds__(NTT_BLOCK) k_ntt_group(const uint32_t* src, ui
 #if MNT753_NTT_LAZY
       // Carry-free butterflies (the lazy arithmetic of the pairing levels, fp753.hip.h): x_lo +- w x_hi limb-wise with signed limbs
       // (54 instructions instead of the 540 of fp_add + fp_sub), the product through the signed multiplier, and one normalisation
-      // per element every SECOND stage.  Ranges: stage A takes values in [0, 1.51p) with limbs below 2^28 (fresh from fp_unpack or
-      // fp_norm) and a twiddle in [0, 2p): t in (-0.34p, 1.34p), outputs in (-0.85p, 2.85p) with |limb| < 2^29; stage B takes those:
-      // t in (-0.63p, 1.63p), outputs in (-2.48p, 4.48p) with |limb| < 2^29.6 -- inside what fp_norm accepts (|value| < 5p,
-      // |limb| < 2^30), which returns them to [0.49p, 1.51p).  Values mod p are those of the eager form.
+      // per element every SECOND stage.  Ranges (p / R' < 0.1106 for both moduli): stage A takes values in [0, 1.51p) with limbs
+      // below 2^28 (fresh from fp_unpack or fp_norm) and a twiddle in [0, 2p): t in [0, 1.34p), outputs in (-1.34p, 2.85p) with
+      // |limb| < 2^29; stage B takes those: t in (-0.30p, 1.63p), outputs in (-2.97p, 4.48p) with |limb| < 3 * 2^28.  The first
+      // stage of the transform (s0 + q == 0, below) takes t = x_hi itself, in [0, 1.51p): its outputs lie in (-1.51p, 3.02p), and
+      // the stage B behind it gives t in (-0.34p, 1.67p), outputs in (-3.18p, 4.69p) with |limb| < 3 * 2^28.  All of it inside what
+      // fp_norm accepts (|value| < 5p; |limb| + 2^28 |q| < 2^31 - 2^4 with |q| <= 4 here), which returns them to [0.49p, 1.51p).
+      // Values mod p are those of the eager form.  (tests/test_field_raw_*.py assert these ranges, both first-stage forms, at
+      // their edges.)
       if (s0 + q == 0) {
         t = xh;                                        // the first stage's only twiddle is omega^0 (block-uniform: one product in twenty saved)
       } else {
