@@ -1,17 +1,25 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X Groth16 prover hot path (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
-BASELINE.json's metric has two halves and the ONE JSON line rank 0 prints carries both:
+A plain run does what the headline figure needs and nothing else: it builds the benchmark input and its base set, runs W warm-up
+and K timed steps, writes the result of the last step (--dump-outputs) and prints ONE JSON line (rank 0):
 
   * `value` -- G1 MSM points/sec at 2^20 (MNT4753, configs[1]).  One process per GPU; a step is ONE multi-scalar
     multiplication over 2^20 (base, scalar) pairs, bases (with their window table) and scalars resident in HBM.  N > 1 is
     the north-star split: the ONE 2^20 array is cut into N contiguous slices (multiexp.tcc:417-431), rank g runs the whole
     Pippenger on slice g, and the only exchange the path has follows -- an all_gather (RCCL over xGMI) of one 288-byte
     projective point per rank and the serial fold of the N partial sums (multiexp.tcc:433-438).  Total work is fixed
-    ("strong"); the same run also times 2^20 points PER GPU and reports that under `weak`.
+    ("strong").  Beside it, what the timed steps themselves report: `phases_ms`, `precompute_ms` (the base set's window
+    table, built before timing) and `roofline` of the bucket accumulation (its HBM traffic quoted from profiles/ while the
+    kernel sources are the ones it was measured on).
+
+--full adds every other measurement and check to the same line (each --no-* option leaves one leg of it out):
+
+  * `parity_ok` -- the timed result checked through the discrete logs of the synthetic bases (and every other result below
+    against its own known answer); a failure makes the run exit non-zero.  N > 1: `weak`, 2^20 points PER GPU.
   * `prove` -- Groth16 prove time in seconds, MNT4753, full-size parameters (configs[3]): `main_hip MNT4753 compute` (the
     C++ host over the C ABI) on the seeded synthetic files of tools/synth_files.py, timed by the prover itself with the
     reference's window ("Total time from input to output", libsnark/main.cpp:203-270) and by this script around the
@@ -24,9 +32,11 @@ BASELINE.json's metric has two halves and the ONE JSON line rank 0 prints carrie
   * `exchange_us` -- the one exchange the sharded path has (multiexp.tcc:433-438: one projective point per rank, then the serial fold)
     over RCCL: mean latency of 100 all_gathers of a G1 point through parallel.PointExchange (host -> device -> all_gather -> host).
     N = 1: a world-size-1 RCCL communicator in a child process; N > 1: the communicator of the run itself.
+  * `cpu_baseline` -- the reference's multi_exp on the benchmark input, its result compared with the timed one (N = 1), and
+    `roofline.traffic` measured by two rocprofv3 --pmc passes of their own (child processes, N = 1).
 
-Secondary figures on the same line (N = 1): 2^20 FFT and compute_H (configs[2]), the G2 MSM at 2^20, the G1 MSM without
-the window table and the one-off cost of building the table, `roofline` for the dominant kernels and `cpu_baseline`.
+Secondary figures on the same line (N = 1, --full): 2^20 FFT and compute_H (configs[2]) as `roofline_fft`, the G2 MSM at 2^20,
+the G1 MSM without the window table, the slice sizes of an N-way split and the prove times predicted from them (`extras`).
 
 PyTorch is plumbing here (device memory for the scalars, streams/events, torch.distributed); every kernel is in
 libmnt753_hip.so, reached through the C ABI.  oracle/ is used only for the cpu_baseline leg.
@@ -198,8 +208,7 @@ def live_traffic():
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="bench_pmc_", dir="/tmp")
         try:
-            cmd = ["rocprofv3", "--pmc", ctr, "-d", d, "-o", "pmc", "--", sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1",
-                   "--no-cpu-baseline", "--no-prove", "--no-extras", "--no-traffic", "--no-exchange"]
+            cmd = ["rocprofv3", "--pmc", ctr, "-d", d, "-o", "pmc", "--", sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1"]
             r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), capture_output=True, text=True, timeout=600)
             dbs = glob.glob(os.path.join(d, "**", "*_results.db"), recursive=True)
             if r.returncode != 0 or not dbs:
@@ -483,13 +492,16 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--log-n", type=int, default=LOG_N, help="log2 of the bases per GPU (benchmark config: 20)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prove", action="store_true", help="skip the full-prove leg (N = 1 runs it by default)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the FFT / compute_H / G2 / table-less legs")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc passes that measure the HBM traffic of the dominant phase")
-    ap.add_argument("--no-exchange", action="store_true", help="skip the RCCL exchange-latency leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other leg and check of the line (parity, prove legs, CPU baselines, RCCL exchange, "
+                         "live PMC traffic, extras, weak scaling; see the module docstring); a plain run only sets up, times and reports the steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU MSM baseline")
+    ap.add_argument("--no-prove", action="store_true", help="--full without the full-prove legs")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the FFT / compute_H / G2 / table-less legs")
+    ap.add_argument("--no-traffic", action="store_true", help="--full without the two rocprofv3 --pmc passes that measure the HBM traffic of the dominant phase")
+    ap.add_argument("--no-exchange", action="store_true", help="--full without the RCCL exchange-latency leg")
     ap.add_argument("--prove-log2-d", type=int, nargs=2, default=None, metavar=("MNT4753", "MNT6753"),
-                    help="sizes of the prove legs (default 20 15 = the metric's; tests pass sizes with a minted hash, e.g. 14 10); runs them whatever --log-n is")
+                    help="sizes of the prove legs of --full (default 20 15 = the metric's; tests pass sizes with a minted hash, e.g. 14 10); runs them whatever --log-n is")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the MSM result of the last one as DIR/msm_affine.npy (see dump_outputs)")
     ap.add_argument("--exchange-probe", action="store_true", help=argparse.SUPPRESS)
@@ -519,7 +531,7 @@ def main():
     # `main_hip ... --gpus N` (one process over the N devices); the other ranks wait on a CPU-side barrier -- a file named after the
     # launcher (same parent process and rendezvous port for all ranks of one launch).
     legs = None
-    want_prove = not args.no_prove and not under_profiler and (args.log_n == LOG_N or args.prove_log2_d is not None)
+    want_prove = args.full and not args.no_prove and not under_profiler and (args.log_n == LOG_N or args.prove_log2_d is not None)
     d4, d6 = args.prove_log2_d if args.prove_log2_d else (20, 15)
     if want_prove and world == 1:
         legs = prove_legs() if args.prove_log2_d is None else {"prove": prove_leg(d4, "MNT4753")[0], "prove_mnt6753": prove_leg(d6, "MNT6753")[0], "cpu_prove": []}
@@ -548,10 +560,10 @@ def main():
             if open(gate).read().strip() != "ok":
                 raise SystemExit("bench.py: rank 0's prove legs failed; this rank leaves before it touches a GPU")
     exchange = None
-    if world == 1 and not args.no_exchange and args.log_n == LOG_N and not under_profiler:
+    if args.full and world == 1 and not args.no_exchange and args.log_n == LOG_N and not under_profiler:
         exchange = exchange_leg()
     traffic_live = None
-    if world == 1 and not args.no_traffic and args.log_n == LOG_N and not under_profiler:   # (a profiled run has the GPU initialised already)
+    if args.full and world == 1 and not args.no_traffic and args.log_n == LOG_N and not under_profiler:   # (a profiled run has the GPU initialised already)
         traffic_live = live_traffic()
 
     import numpy as np
@@ -620,7 +632,7 @@ def main():
     out, elapsed, tot_ms = timed(step, args.steps, args.warmup)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, pkg, np, out)
-    if world > 1:
+    if args.full and world > 1:
         try:
             exchange = dict(time_exchange(pkg, comm_dev), world_size=world, backend=dist.get_backend(),
                             note="the run's own communicator: " + ("gloo on a shared GPU (development)" if share else "RCCL, one rank per GPU over xGMI"))
@@ -628,13 +640,15 @@ def main():
             exchange = {"error": repr(ex)[:300]}
     acc_ms = [t["accumulate_ms"] for t in tot_ms]
     plan = pkg.msm_last_plan()
-    # parity of what was just timed: the whole array through its discrete logs (one host scalar multiplication)
-    exp = pkg.synth_expected_msm(0, 1, 42, sc)
-    ok = bool(np.array_equal(pkg.point_to_affine(0, 1, out), pkg.point_to_affine(0, 1, exp)))
+    ok = True   # the checks of --full; a plain run makes none
+    if args.full:
+        # parity of what was just timed: the whole array through its discrete logs (one host scalar multiplication)
+        exp = pkg.synth_expected_msm(0, 1, 42, sc)
+        ok = bool(np.array_equal(pkg.point_to_affine(0, 1, out), pkg.point_to_affine(0, 1, exp)))
 
     # weak scaling beside it (N > 1): 2^log_n points PER GPU, rank g with its own array, same exchange and fold
     weak = None
-    if world > 1:
+    if args.full and world > 1:
         bases.close()
         pts_w = pkg.synth_points(0, 1, 42 + 1000 * rank, n) if rank else pts
         sc_w = pkg.synth_scalars(0, 43 + 1000 * rank, n) if rank else sc
@@ -705,7 +719,6 @@ def main():
             "vs_baseline": None,
             "dtype": "u32x27 limbs / u64 columns",
             "data": "synthetic",
-            "parity_ok": ok,
             "config": {"workload": f"MNT4753 G1 Pippenger MSM, 2^{args.log_n} bases" + (f" split into {world} contiguous slices (one per GPU)" if world > 1 else "") +
                                    ", bit-exact vs libff::multi_exp",
                        "curve": "MNT4753", "group": "G1", "points": n, "points_per_gpu": n_local, "window_bits": plan_c, "windows": windows,
@@ -737,7 +750,7 @@ def main():
                 line["exchange_us"] = exchange["g1_point"]["mean_us"]
 
     if world == 1:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             base, got, n2 = cpu_baseline(pkg, pts, sc, np)
             if n2 == n:      # the reference ran the whole benchmark input: compare with the result of the timed loop itself
                 same = bool(np.array_equal(pkg.point_to_affine(0, 1, out), got))
@@ -748,7 +761,7 @@ def main():
             base["matches_gpu_on_sample"] = same
             line["cpu_baseline"] = base
             ok = ok and same
-        if not args.no_extras and args.log_n == LOG_N:
+        if args.full and not args.no_extras and args.log_n == LOG_N:
             extras = {}
             # G1 MSM without the window table (what a caller pays who cannot keep 8.9 GB per base set resident)
             os.environ["MNT753_MSM_PRECOMP"] = "0"
@@ -934,12 +947,12 @@ def main():
             for c in legs["cpu_prove"]:
                 if c.get("same_bytes_as_gpu") is False:
                     ok = False
-        line["parity_ok"] = ok
     elif rank == 0 and legs is not None:
         line.update(legs)
         ok = ok and bool(legs["prove"].get("parity_ok")) and bool(legs["prove_mnt6753"].get("parity_ok"))
-        line["parity_ok"] = ok
     if rank == 0:
+        if args.full:
+            line["parity_ok"] = ok
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

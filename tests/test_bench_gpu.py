@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,7 +20,7 @@ def test_bench_multi_rank_flow(gpu, world):
     # --prove-log2-d 14 10: the prove legs at the reference generator's `fast` sizes, for which tests/golden/oracle_hashes.json holds the
     # reference's proofs (the driver's run uses the metric's own 2^20 / 2^15)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--log-n", "13",
-                        "--prove-log2-d", "14", "10"], capture_output=True, text=True, env=env, timeout=1500)
+                        "--full", "--prove-log2-d", "14", "10"], capture_output=True, text=True, env=env, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -52,7 +53,7 @@ def test_bench_multi_rank_flow(gpu, world):
 
 def test_bench_single_gpu_contract_small(gpu):
     """The N = 1 line at a small size: every field of the contract, no prove / extras legs (those need the 2^20 workload)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--log-n", "13", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--log-n", "13", "--full", "--no-cpu-baseline",
                         "--prove-log2-d", "14", "10"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -65,3 +66,28 @@ def test_bench_single_gpu_contract_small(gpu):
     one = j["prove"]["one_shot"]
     assert one["same_bytes"] is True and one["one_shot_policy_applied"] is True and j["prove"]["one_shot_wall_s"] == one["wall_incl_params_s"] > 0
     assert j["roofline"]["bound"].startswith("int-mad") and j["roofline"]["modmul_peak_first_principles_per_s"] > j["roofline"]["modmul_peak_per_s"]
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_bench_plain_run(gpu, world, tmp_path):
+    """Without --full the run times the steps and reports them, nothing else: none of the legs or checks of --full is in the line,
+    and --dump-outputs writes the MSM of the last timed step, here checked through the discrete logs of the synthetic bases."""
+    env = dict(os.environ, BENCH_SHARE_GPU="1") if world > 1 else dict(os.environ)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--log-n", "13",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["n_gpus"] == world and j["steps"] == 2 and j["warmup"] == 1 and j["scaling"] == "strong"
+    assert j["unit"] == "points/s" and j["higher_is_better"] is True and j["value"] == pytest.approx((1 << 13) * 1e3 / j["ms_per_step"])
+    for key in ("metric", "dtype", "config", "roofline", "phases_ms", "precompute_ms"):
+        assert key in j
+    for key in ("parity_ok", "weak", "prove", "prove_mnt6753", "cpu_prove", "cpu_baseline", "exchange", "exchange_us", "extras",
+                "no_window_table", "roofline_fft"):
+        assert key not in j, key
+    got = np.load(tmp_path / "msm_affine.npy")
+    assert got.shape == (2, 12, 2)
+    words = got[..., 0].astype(np.uint64) | (got[..., 1].astype(np.uint64) << np.uint64(32))
+    exp = gpu.point_to_affine(0, 1, gpu.synth_expected_msm(0, 1, 42, gpu.synth_scalars(0, 43, 1 << 13)))
+    assert np.array_equal(words.reshape(-1), exp)

@@ -4,19 +4,19 @@
 #   guide prescribes), kernel stats of a G2 MSM, and the full-size proves.  usage: tools/collect_profiles.sh
 cd "$(dirname "$0")/.."
 R=$PWD; O=$R/gpurun_out/prof; mkdir -p $O
-python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_stderr.log
+python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_stderr.log
 # round 3: the slice sweep behind pair_levels() and the predicted 1/2/4/8-GPU curve, board power / clocks under load, the compiler
 # reproducers, and the N > 1 flow of bench.py on the shared device (gloo)
 python3 tools/slice_sweep.py --out $O/slice_sweep.json > $O/slice_sweep.log 2>&1
 sh tools/experiments/power_sample.sh > $O/power_and_clocks.txt 2>&1
 sh tools/compiler_repro/check.sh > $O/compiler_repro.log 2>&1
-BENCH_SHARE_GPU=1 python3 bench.py --gpus 4 --steps 5 --warmup 2 > $O/bench_4ranks_shared_gpu.json 2>/dev/null
+BENCH_SHARE_GPU=1 python3 bench.py --full --gpus 4 --steps 5 --warmup 2 > $O/bench_4ranks_shared_gpu.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 # exactly the timed loop of the driver's command (20 steps + 5 warm-up of the table-mode 2^20 G1 MSM, nothing else): the per-kernel
 # averages of kt_loop are what `roofline.kernel_ms` and the per-kernel table of DESIGN.md 4.3 must agree with
 rocprofv3 --kernel-trace --stats -d $O/kt_loop -o bench -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-prove --no-extras --no-traffic > $O/bench_loop_under_rocprof.json 2>/dev/null
 # the other legs (table-less MSM, FFT / compute_H, G2, slice sweep) in a trace of their own
-rocprofv3 --kernel-trace --stats -d $O/kt_extras -o bench -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-prove --no-traffic > $O/bench_extras_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $O/kt_extras -o bench -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-prove --no-traffic > $O/bench_extras_under_rocprof.json 2>/dev/null
 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o bench -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-prove --no-extras --no-traffic > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write -o bench -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-prove --no-extras --no-traffic > /dev/null 2>&1
 CURVE=0 GROUP=2 rocprofv3 --kernel-trace --stats -d $O/kt_g2 -o g2 -- python3 $R/tools/dev_msm_big.py 20 3 > $O/g2_msm_2p20.log 2>/dev/null
