@@ -41,7 +41,7 @@ extern "C" {
 #define MNT753_ENODEV (-2)   /* no HIP device / library not initialised */
 #define MNT753_EHIP (-3)     /* a HIP runtime call failed */
 #define MNT753_ENOMEM (-4)   /* device or host allocation failed */
-#define MNT753_EDOMAIN (-5)  /* FFT size is not a supported power of two for this field */
+#define MNT753_EDOMAIN (-5)  /* no supported evaluation domain of this size for this field */
 #define MNT753_ESELFTEST (-6) /* mnt753_self_test: a known-answer check failed -- this build must not be used to prove */
 
 /* FFT kinds: libfqfft basic_radix2_domain::{FFT,iFFT,cosetFFT,icosetFFT}
@@ -196,8 +196,21 @@ int mnt753_point_from_affine(int curve, int group, const uint64_t* affine, uint6
 
 /* ---- FFT over Fr ---------------------------------------------------------------------------------- */
 typedef struct mnt753_domain mnt753_domain;
-/* replaces B::get_evaluation_domain (hpp:30): m must be a power of two <= 2^s (s = 30 MNT4753, 15 MNT6753) */
+/* libfqfft's basic_radix2_domain of exactly m elements: m must be a power of two <= 2^s (s = 30 MNT4753, 15 MNT6753),
+ * MNT753_EDOMAIN otherwise.  (B::get_evaluation_domain goes through mnt753_domain_create_for.) */
 int mnt753_domain_create(int curve, size_t m, mnt753_domain** out);
+/* replaces B::get_evaluation_domain (hpp:30) = libfqfft get_evaluation_domain(min_size): the first of basic_radix2_domain,
+ * extended_radix2_domain (2^(s+1): two size-2^s transforms, the second on the coset shift * <omega>) and step_radix2_domain
+ * (2^k + 2^r) that accepts min_size, then the same three at big + rounded_small, which may be larger than min_size
+ * (mnt753_domain_size says).  Every call that takes a domain works on all three kinds.  MNT753_EDOMAIN, with a message naming
+ * the size and the reference's domain, wherever the reference's walk stops at a domain this library does not build: a
+ * mixed-radix basic domain (MNT6753 only: its Fr accepts 2^a 5^b, a <= 15, b <= 2, so 5, 10, 25, 40, 5 * 2^15 are refused,
+ * not stepped) or the candidates behind the first six (mixed-radix best fit, geometric and arithmetic sequence domains). */
+#define MNT753_DOMAIN_BASIC 0
+#define MNT753_DOMAIN_EXTENDED 1
+#define MNT753_DOMAIN_STEP 2
+int mnt753_domain_create_for(int curve, size_t min_size, mnt753_domain** out);
+int mnt753_domain_kind(const mnt753_domain* d);      /* MNT753_DOMAIN_*; -1 for a null domain */
 int mnt753_domain_free(mnt753_domain* d);
 size_t mnt753_domain_size(const mnt753_domain* d);   /* B::domain_get_m (hpp:47) */
 /* replaces B::domain_iFFT / domain_cosetFFT / domain_icosetFFT (hpp:42-45) and libfqfft FFT; in place on

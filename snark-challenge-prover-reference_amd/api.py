@@ -78,6 +78,8 @@ def lib():
         "mnt753_point_to_affine": (i, [i, i, u64p, u64p]),
         "mnt753_point_from_affine": (i, [i, i, u64p, u64p]),
         "mnt753_domain_create": (i, [i, sz, C.POINTER(vp)]),
+        "mnt753_domain_create_for": (i, [i, sz, C.POINTER(vp)]),
+        "mnt753_domain_kind": (i, [vp]),
         "mnt753_domain_free": (i, [vp]),
         "mnt753_domain_size": (sz, [vp]),
         "mnt753_fft": (i, [vp, i, vp, vp]),
@@ -316,12 +318,30 @@ class DeviceBuffer:
 
 
 class Domain:
-    """basic_radix2_domain over Fr of the curve (B::get_evaluation_domain)."""
+    """An evaluation domain over Fr of the curve.  Domain(curve, m): libfqfft's basic_radix2_domain of exactly m elements (a power of
+    two).  Domain.for_size(curve, min_size): the domain libfqfft's get_evaluation_domain(min_size) builds (B::get_evaluation_domain) --
+    basic, extended (2^(s+1)) or step (2^k + 2^r) radix-2; its size `m` may be larger than min_size."""
+
+    BASIC, EXTENDED, STEP = 0, 1, 2
 
     def __init__(self, curve, m):
         self.curve, self.m = curve, int(m)
         self._h = C.c_void_p()
         _check(lib().mnt753_domain_create(curve, self.m, C.byref(self._h)), "mnt753_domain_create")
+
+    @classmethod
+    def for_size(cls, curve, min_size):
+        self = cls.__new__(cls)
+        self.curve = curve
+        self._h = C.c_void_p()
+        _check(lib().mnt753_domain_create_for(curve, int(min_size), C.byref(self._h)), "mnt753_domain_create_for")
+        self.m = int(lib().mnt753_domain_size(self._h))
+        return self
+
+    @property
+    def kind(self):
+        """Domain.BASIC, Domain.EXTENDED or Domain.STEP."""
+        return int(lib().mnt753_domain_kind(self._h))
 
     def fft(self, kind, dev_ptr, stream=None):
         st = C.c_void_p(int(stream)) if stream else C.c_void_p()

@@ -1,6 +1,8 @@
 // FFT part of the C ABI (include/mnt753_hip.h): evaluation domains, the four transform kinds,
 // divide_by_Z_on_coset, the element-wise vector ops and the device-resident compute_H.
 #include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -26,12 +28,25 @@ struct mnt753_domain {
   hipEvent_t work_free = nullptr;                      // recorded after every transform: the next user of `work` (any stream) waits for it
   uint32_t *stage = nullptr;                           // the seeds the tables were generated from (freed with the domain:
                                                        // hipFree is a device-wide sync and would wait for MSMs in flight)
+  // step (m = big_m + small_m) and extended (m = 2 small_m, big_m = small_m) domains: two inner basic domains and the tables of
+  // the passes around them (ntt_kernels.hip.h).  Of the fields above they use m, work, work_free and stage only.
+  int kind = MNT753_DOMAIN_BASIC;
+  size_t big_m = 0, small_m = 0;
+  mnt753_domain *sub_big = nullptr, *sub_small = nullptr;   // sizes big_m and small_m (sub_small: null where small_m is 1; extended: both the same object)
+  uint32_t *x_fwd = nullptr;                           // step: omega^k (big_m)                 extended: shift^i (small_m)
+  uint32_t *x_inv = nullptr;                           // step: omega^k / (2 big_m) (big_m)     extended: sconst shift^-i (small_m)
+  uint32_t *x_inv2 = nullptr;                          // step: omega^-i (small_m)
+  uint32_t *xcos_fwd = nullptr, *xcos_inv = nullptr;   // g^k, g^-k (m each)
+  uint32_t *xconsts = nullptr;                         // step: 1/(2 big_m), 1/(2 small_m), 1/big_m, 2^12    extended: shift^s, sconst, -, 2^12
+  uint32_t *zt = nullptr, *zt12 = nullptr;             // 1/Z on the coset and 2^-12 times it: z_mask + 2 entries each (z_index)
+  size_t z_split = 0, z_mask = 0;
 };
 
 namespace {
 
+// inner: the domain serves a step or extended domain, which brings its own coset tables
 template <int M>
-int build_tables(mnt753_domain* d) {
+int build_tables(mnt753_domain* d, bool inner = false) {
   typedef HFp<M> Fr;
   const size_t m = d->m;
   const int logm = d->logm;
@@ -61,9 +76,11 @@ int build_tables(mnt753_domain* d) {
   const size_t half = m / 2 ? m / 2 : 1;
   HIP_TRY(hipMalloc(&d->tw_fwd, half * FPS_WORDS * 4));
   HIP_TRY(hipMalloc(&d->tw_inv, half * FPS_WORDS * 4));
-  HIP_TRY(hipMalloc(&d->cos_fwd, m * FPS_WORDS * 4));
-  HIP_TRY(hipMalloc(&d->cos_fwd_s, m * FPS_WORDS * 4));
-  HIP_TRY(hipMalloc(&d->cos_inv_s, m * FPS_WORDS * 4));
+  if (!inner) {
+    HIP_TRY(hipMalloc(&d->cos_fwd, m * FPS_WORDS * 4));
+    HIP_TRY(hipMalloc(&d->cos_fwd_s, m * FPS_WORDS * 4));
+    HIP_TRY(hipMalloc(&d->cos_inv_s, m * FPS_WORDS * 4));
+  }
   HIP_TRY(hipMalloc(&d->consts, 4 * FPS_WORDS * 4));
   HIP_TRY(hipMalloc(&d->work, m * 96));
   auto table = [&](uint32_t* out, int base_slot, int scale_slot, size_t n) {
@@ -72,9 +89,11 @@ int build_tables(mnt753_domain* d) {
   };
   table(d->tw_fwd, 0, 128, half);
   table(d->tw_inv, 1, 128, half);
-  table(d->cos_fwd, 2, 128, m);
-  table(d->cos_fwd_s, 2, 129, m);
-  table(d->cos_inv_s, 3, 129, m);
+  if (!inner) {
+    table(d->cos_fwd, 2, 128, m);
+    table(d->cos_fwd_s, 2, 129, m);
+    table(d->cos_inv_s, 3, 129, m);
+  }
   hipLaunchKernelGGL((k_consts_to_internal<M>), dim3(1), dim3(64), 0, 0, d->consts, d_stage + (size_t)132 * 24, 4);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(nullptr));   // the tables are built on the default stream; MSM streams are not waited for
@@ -83,16 +102,18 @@ int build_tables(mnt753_domain* d) {
 
 // bit-reversal + log2 m butterfly stages, in place on `vec` (via the domain's work buffer)
 // in_scale / out_scale: tables the elements are multiplied by on the way into the first group / out of the last (k_ntt_group)
+// (from / vec: the transform reads `from` and leaves its result in `vec`; they are the same vector or do not overlap)
 template <int M>
-int run_stages(mnt753_domain* d, uint32_t* vec, const uint32_t* tw, hipStream_t st, const uint32_t* in_scale = nullptr, const uint32_t* out_scale = nullptr) {
+int run_stages(mnt753_domain* d, const uint32_t* from, uint32_t* vec, const uint32_t* tw, hipStream_t st, const uint32_t* in_scale = nullptr, const uint32_t* out_scale = nullptr) {
   const int logm = d->logm;
+  const bool in_place = from == vec;
   if (logm == 0) return 0;
   int n_groups = (logm + NTT_MAX_NS - 1) / NTT_MAX_NS;
   int s0 = 0;
   for (int gi = 0; gi < n_groups; ++gi) {
     int ns = (logm - s0 + (n_groups - gi) - 1) / (n_groups - gi);   // balanced split
-    const uint32_t* src = gi == 0 ? vec : d->work;
-    uint32_t* dst = (gi == n_groups - 1 && n_groups > 1) ? vec : d->work;
+    const uint32_t* src = gi == 0 ? from : d->work;
+    uint32_t* dst = (gi == n_groups - 1 && (n_groups > 1 || !in_place)) ? vec : d->work;
     const size_t n_tiles = (size_t)1 << (logm - ns);
     const int tiles_per_block = NTT_BLOCK / (1 << (ns - 1));
     const unsigned blocks = (unsigned)((n_tiles + tiles_per_block - 1) / tiles_per_block);
@@ -106,7 +127,57 @@ int run_stages(mnt753_domain* d, uint32_t* vec, const uint32_t* tw, hipStream_t 
     else hipLaunchKernelGGL((k_ntt_group<M, false, false>), dim3(blocks), dim3(NTT_BLOCK), 0, st, src, dst, tw, logm, s0, ns, bitrev, is, os);
     s0 += ns;
   }
-  if (n_groups == 1) HIP_TRY(hipMemcpyAsync(vec, d->work, d->m * 96, hipMemcpyDeviceToDevice, st));
+  if (n_groups == 1 && in_place) HIP_TRY(hipMemcpyAsync(vec, d->work, d->m * 96, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- step and extended domains: the passes of ntt_kernels.hip.h around the inner transforms --------------------------------------
+struct StepGrid { unsigned blocks, threads; int ti_n, tj_n; };
+// k_step_pre / k_step_post: ti_n = min(small_m, 64) outputs per block, tj_n = min(compr, 256 / ti_n) partial sums per output
+inline StepGrid step_grid(const mnt753_domain* d) {
+  const size_t compr = d->big_m / d->small_m;
+  const int ti_n = (int)(d->small_m < 64 ? d->small_m : 64);
+  const int tj_n = (int)(compr < (size_t)(256 / ti_n) ? compr : (size_t)(256 / ti_n));
+  return StepGrid{(unsigned)(d->small_m / ti_n), (unsigned)(ti_n * tj_n), ti_n, tj_n};
+}
+// the two inner transforms, from one buffer into the other (a size-1 transform is a copy)
+template <int M>
+int x_inner(mnt753_domain* d, const uint32_t* from, uint32_t* to, bool inverse, hipStream_t st) {
+  mnt753_domain *b = d->sub_big, *sm = d->sub_small;
+  if (int rc = run_stages<M>(b, from, to, inverse ? b->tw_inv : b->tw_fwd, st)) return rc;
+  if (sm) return run_stages<M>(sm, from + d->big_m * 24, to + d->big_m * 24, inverse ? sm->tw_inv : sm->tw_fwd, st);
+  HIP_TRY(hipMemcpyAsync(to + d->big_m * 24, from + d->big_m * 24, 96, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+// FFT (coset: cosetFFT), in place on vec through the domain's work buffer
+template <int M>
+int x_forward(mnt753_domain* d, uint32_t* vec, bool coset, hipStream_t st) {
+  if (d->kind == MNT753_DOMAIN_STEP) {
+    const StepGrid g = step_grid(d);
+    if (coset) hipLaunchKernelGGL((k_step_pre<M, true>), dim3(g.blocks), dim3(g.threads), 0, st, vec, d->work, d->x_fwd, d->xcos_fwd, d->big_m, d->small_m, g.ti_n, g.tj_n);
+    else hipLaunchKernelGGL((k_step_pre<M, false>), dim3(g.blocks), dim3(g.threads), 0, st, vec, d->work, d->x_fwd, d->xcos_fwd, d->big_m, d->small_m, g.ti_n, g.tj_n);
+  } else {
+    const unsigned gb = (unsigned)((d->small_m + 255) / 256);
+    if (coset) hipLaunchKernelGGL((k_ext_pre<M, true>), dim3(gb), dim3(256), 0, st, vec, d->work, d->x_fwd, d->xcos_fwd, d->xconsts, d->small_m);
+    else hipLaunchKernelGGL((k_ext_pre<M, false>), dim3(gb), dim3(256), 0, st, vec, d->work, d->x_fwd, d->xcos_fwd, d->xconsts, d->small_m);
+  }
+  HIP_TRY(hipGetLastError());
+  return x_inner<M>(d, d->work, vec, false, st);
+}
+// iFFT (coset: icosetFFT)
+template <int M>
+int x_inverse(mnt753_domain* d, uint32_t* vec, bool coset, hipStream_t st) {
+  if (int rc = x_inner<M>(d, vec, d->work, true, st)) return rc;
+  if (d->kind == MNT753_DOMAIN_STEP) {
+    const StepGrid g = step_grid(d);
+    if (coset) hipLaunchKernelGGL((k_step_post<M, true>), dim3(g.blocks), dim3(g.threads), 0, st, d->work, vec, d->x_inv, d->x_inv2, d->xcos_inv, d->xconsts, d->big_m, d->small_m, g.ti_n, g.tj_n);
+    else hipLaunchKernelGGL((k_step_post<M, false>), dim3(g.blocks), dim3(g.threads), 0, st, d->work, vec, d->x_inv, d->x_inv2, d->xcos_inv, d->xconsts, d->big_m, d->small_m, g.ti_n, g.tj_n);
+  } else {
+    const unsigned gb = (unsigned)((d->small_m + 255) / 256);
+    if (coset) hipLaunchKernelGGL((k_ext_post<M, true>), dim3(gb), dim3(256), 0, st, d->work, vec, d->x_inv, d->xcos_inv, d->xconsts, d->small_m);
+    else hipLaunchKernelGGL((k_ext_post<M, false>), dim3(gb), dim3(256), 0, st, d->work, vec, d->x_inv, d->xcos_inv, d->xconsts, d->small_m);
+  }
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -114,18 +185,27 @@ int run_stages(mnt753_domain* d, uint32_t* vec, const uint32_t* tw, hipStream_t 
 template <int M>
 int fft_t(mnt753_domain* d, int kind, uint32_t* vec, hipStream_t st) {
   const size_t m = d->m;
+  if (d->kind != MNT753_DOMAIN_BASIC) {
+    switch (kind) {
+      case MNT753_FFT: return x_forward<M>(d, vec, false, st);
+      case MNT753_IFFT: return x_inverse<M>(d, vec, false, st);
+      case MNT753_COSET_FFT: return x_forward<M>(d, vec, true, st);
+      case MNT753_ICOSET_FFT: return x_inverse<M>(d, vec, true, st);
+      default: return set_error(MNT753_EINVAL, "fft: unknown kind");
+    }
+  }
   const unsigned gb = (unsigned)((m + 255) / 256);
   switch (kind) {
     case MNT753_FFT:
-      return run_stages<M>(d, vec, d->tw_fwd, st);
+      return run_stages<M>(d, vec, vec, d->tw_fwd, st);
     case MNT753_IFFT:
-      if (int rc = run_stages<M>(d, vec, d->tw_inv, st)) return rc;
+      if (int rc = run_stages<M>(d, vec, vec, d->tw_inv, st)) return rc;
       hipLaunchKernelGGL((k_vec_mul_const<M>), dim3(gb), dim3(256), 0, st, vec, d->consts, m);
       break;
     case MNT753_COSET_FFT:
-      return run_stages<M>(d, vec, d->tw_fwd, st, d->cos_fwd, nullptr);
+      return run_stages<M>(d, vec, vec, d->tw_fwd, st, d->cos_fwd, nullptr);
     case MNT753_ICOSET_FFT:
-      return run_stages<M>(d, vec, d->tw_inv, st, nullptr, d->cos_inv_s);
+      return run_stages<M>(d, vec, vec, d->tw_inv, st, nullptr, d->cos_inv_s);
     default:
       return set_error(MNT753_EINVAL, "fft: unknown kind");
   }
@@ -139,16 +219,25 @@ int fft_t(mnt753_domain* d, int kind, uint32_t* vec, hipStream_t st) {
 // x -> cosetFFT(iFFT(x)) = stages(inv), *(g^i/m), stages(fwd)
 template <int M>
 int h_chain_t(mnt753_domain* d, uint32_t* vec, hipStream_t st) {
-  if (int rc = run_stages<M>(d, vec, d->tw_inv, st)) return rc;
-  return run_stages<M>(d, vec, d->tw_fwd, st, d->cos_fwd_s, nullptr);      // (g^i / m) rides on the forward transform's first pass
+  if (d->kind != MNT753_DOMAIN_BASIC) {
+    if (int rc = x_inverse<M>(d, vec, false, st)) return rc;
+    return x_forward<M>(d, vec, true, st);
+  }
+  if (int rc = run_stages<M>(d, vec, vec, d->tw_inv, st)) return rc;
+  return run_stages<M>(d, vec, vec, d->tw_fwd, st, d->cos_fwd_s, nullptr);      // (g^i / m) rides on the forward transform's first pass
 }
 // a = (a*b - c)/Z ; a = icosetFFT(a) ; h = a | 0
 template <int M>
 int h_finish_t(mnt753_domain* d, uint32_t* ca, const uint32_t* cb, const uint32_t* cc, uint32_t* h, hipStream_t st) {
   const size_t m = d->m;
   const unsigned gb = (unsigned)((m + 255) / 256);
-  hipLaunchKernelGGL((k_h_pointwise<M>), dim3(gb), dim3(256), 0, st, ca, cb, cc, d->consts + 1 * FPS_WORDS, d->consts + 2 * FPS_WORDS, m);
-  if (int rc = run_stages<M>(d, ca, d->tw_inv, st, nullptr, d->cos_inv_s)) return rc;
+  if (d->kind != MNT753_DOMAIN_BASIC) {
+    hipLaunchKernelGGL((k_h_pointwise_ztab<M>), dim3(gb), dim3(256), 0, st, ca, cb, cc, d->xconsts + 3 * FPS_WORDS, d->zt12, d->z_split, d->z_mask, m);
+    if (int rc = x_inverse<M>(d, ca, true, st)) return rc;
+  } else {
+    hipLaunchKernelGGL((k_h_pointwise<M>), dim3(gb), dim3(256), 0, st, ca, cb, cc, d->consts + 1 * FPS_WORDS, d->consts + 2 * FPS_WORDS, m);
+    if (int rc = run_stages<M>(d, ca, ca, d->tw_inv, st, nullptr, d->cos_inv_s)) return rc;
+  }
   const size_t quads = m * 6 + 6;
   hipLaunchKernelGGL(k_copy_h, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, h, ca, m);
   HIP_TRY(hipGetLastError());
@@ -160,6 +249,226 @@ int compute_h_t(mnt753_domain* d, uint32_t* ca, uint32_t* cb, uint32_t* cc, uint
   for (int v = 0; v < 3; ++v)
     if (int rc = h_chain_t<M>(d, vecs[v], st)) return rc;
   return h_finish_t<M>(d, ca, cb, cc, h, st);
+}
+
+int ceil_log2(size_t n) {            // libff::log2
+  int r = 0;
+  while (r < 64 && ((size_t)1 << r) < n) ++r;
+  return r;
+}
+bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
+
+int create_basic(int curve, int frm, size_t m, bool inner, mnt753_domain** out) {
+  mnt753_domain* d = new (std::nothrow) mnt753_domain();
+  if (!d) return set_error(MNT753_ENOMEM, "domain_create: host allocation failed");
+  d->curve = curve; d->frm = frm; d->m = m; d->logm = ceil_log2(m);
+  d->device = current_physical_device(); d->logical_device = mnt753_get_device();
+  OnDevice on(d->device);
+  int rc = frm == MOD_A ? build_tables<MOD_A>(d, inner) : build_tables<MOD_B>(d, inner);
+  if (rc) { mnt753_domain_free(d); return rc; }
+  *out = d;
+  return 0;
+}
+
+// tables of a step / extended domain (d->kind, big_m, small_m set; the inner domains exist)
+template <int M>
+int build_outer(mnt753_domain* d) {
+  typedef HFp<M> Fr;
+  const size_t m = d->m, big_m = d->big_m, small_m = d->small_m;
+  const bool step = d->kind == MNT753_DOMAIN_STEP;
+  const Fr one = Fr::one();
+  const Fr g = Fr::from_words(FRD[M].mult_gen), g_inv = g.inverse();
+  const Fr two12 = Fr::from_uint(4096), two12_inv = two12.inverse();
+  Fr base_fwd, base_inv, scale_inv, k[4];
+  std::vector<Fr> z;                    // Z on the coset: z_mask + 2 values (z_index)
+  if (step) {
+    // omega: the primitive 2^ceil(log2 m)-th root, order 2 big_m (step_radix2_domain.tcc:21-53)
+    Fr omega = Fr::from_words(FRD[M].root_of_unity);
+    for (int i = FRD[M].two_adicity; i > ceil_log2(m); --i) omega = omega.squared();
+    const Fr half = Fr::from_uint(2).inverse();
+    const Fr binv = Fr::from_uint((uint64_t)big_m).inverse(), sinv = Fr::from_uint((uint64_t)small_m).inverse();
+    base_fwd = omega; base_inv = omega.inverse(); scale_inv = half * binv;
+    k[0] = half * binv; k[1] = half * sinv; k[2] = binv; k[3] = two12;
+    // Z(g x) = (g^big_m - 1)(g^small_m x^small_m - omega^small_m) on x = omega^(2i): x^small_m = (omega^(2 small_m))^i takes
+    // compr values; on x = omega omega_small^i: ((g omega)^big_m - 1)((g omega)^small_m - omega^small_m)     (:252-276)
+    const size_t compr = big_m / small_m;
+    const Fr z0 = g.pow_u64((uint64_t)big_m) - one, gs = g.pow_u64((uint64_t)small_m), os = omega.pow_u64((uint64_t)small_m);
+    const Fr step_w = os.squared(), go = g * omega;
+    Fr elt = one;
+    for (size_t i = 0; i < compr; ++i) { z.push_back(z0 * (gs * elt - os)); elt = elt * step_w; }
+    z.push_back((go.pow_u64((uint64_t)big_m) - one) * (go.pow_u64((uint64_t)small_m) - os));
+    d->z_split = big_m; d->z_mask = compr - 1;
+  } else {
+    // shift = g^2 (libff coset_shift), S = shift^small_m, sconst = 1 / (small_m (1 - S))      (extended_radix2_domain.tcc:48-104)
+    const Fr shift = g.squared(), S = shift.pow_u64((uint64_t)small_m);
+    const Fr sconst = (Fr::from_uint((uint64_t)small_m) * (one - S)).inverse();
+    base_fwd = shift; base_inv = shift.inverse(); scale_inv = sconst;
+    k[0] = S; k[1] = sconst; k[2] = one; k[3] = two12;
+    const Fr gs = g.pow_u64((uint64_t)small_m);             // (:172-191)
+    z.push_back((gs - one) * (gs - S));
+    z.push_back((gs * S - one) * (gs * S - S));
+    d->z_split = small_m; d->z_mask = 0;
+  }
+  // 1 / Z: one inversion for the whole table (Montgomery's trick), on the host, once per domain
+  const size_t nz = z.size();
+  std::vector<Fr> zi(nz);
+  {
+    std::vector<Fr> pre(nz);
+    Fr acc = one;
+    for (size_t i = 0; i < nz; ++i) { pre[i] = acc; acc = acc * z[i]; }
+    Fr inv = acc.inverse();
+    for (size_t i = nz; i-- > 0;) { zi[i] = inv * pre[i]; inv = inv * z[i]; }
+  }
+  // staging (host, wire form): 4 power tables of 32 entries, 2 scales, 4 constants, then 1/Z and 2^-12/Z
+  const size_t z_slot = 4 * 32 + 2 + 4;
+  std::vector<uint64_t> stage((z_slot + 2 * nz) * 12);
+  auto put = [&](size_t slot, const Fr& v) { memcpy(&stage[slot * 12], v.l, 96); };
+  const Fr bases[4] = {base_fwd, base_inv, g, g_inv};
+  for (int t = 0; t < 4; ++t) {
+    Fr p = bases[t];
+    for (int b = 0; b < 32; ++b) { put(t * 32 + b, p); p = p.squared(); }
+  }
+  put(128, one); put(129, scale_inv);
+  for (int i = 0; i < 4; ++i) put(130 + i, k[i]);
+  for (size_t i = 0; i < nz; ++i) { put(z_slot + i, zi[i]); put(z_slot + nz + i, zi[i] * two12_inv); }
+  HIP_TRY(hipMalloc(&d->stage, stage.size() * 8));
+  uint32_t* d_stage = d->stage;
+  HIP_TRY(hipMemcpy(d_stage, stage.data(), stage.size() * 8, hipMemcpyHostToDevice));
+  const size_t n_x = step ? big_m : small_m;
+  HIP_TRY(hipMalloc(&d->x_fwd, n_x * FPS_WORDS * 4));
+  HIP_TRY(hipMalloc(&d->x_inv, n_x * FPS_WORDS * 4));
+  if (step) HIP_TRY(hipMalloc(&d->x_inv2, small_m * FPS_WORDS * 4));
+  HIP_TRY(hipMalloc(&d->xcos_fwd, m * FPS_WORDS * 4));
+  HIP_TRY(hipMalloc(&d->xcos_inv, m * FPS_WORDS * 4));
+  HIP_TRY(hipMalloc(&d->xconsts, 4 * FPS_WORDS * 4));
+  HIP_TRY(hipMalloc(&d->zt, nz * FPS_WORDS * 4));
+  HIP_TRY(hipMalloc(&d->zt12, nz * FPS_WORDS * 4));
+  HIP_TRY(hipMalloc(&d->work, m * 96));
+  const int nbits = ceil_log2(m);
+  auto table = [&](uint32_t* out, int base_slot, int scale_slot, size_t n) {
+    hipLaunchKernelGGL((k_pow_table<M>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, out, d_stage + (size_t)base_slot * 32 * 24,
+                       d_stage + (size_t)scale_slot * 24, n, nbits);
+  };
+  table(d->x_fwd, 0, 128, n_x);
+  if (step) { table(d->x_inv, 0, 129, n_x); table(d->x_inv2, 1, 128, small_m); }
+  else table(d->x_inv, 1, 129, n_x);
+  table(d->xcos_fwd, 2, 128, m);
+  table(d->xcos_inv, 3, 128, m);
+  auto internal = [&](uint32_t* out, size_t slot, size_t n) {
+    hipLaunchKernelGGL((k_consts_to_internal<M>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, out, d_stage + slot * 24, (int)n);
+  };
+  internal(d->xconsts, 130, 4);
+  internal(d->zt, z_slot, nz);
+  internal(d->zt12, z_slot + nz, nz);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return 0;
+}
+
+int create_outer(int curve, int frm, int kind, size_t m, mnt753_domain** out) {
+  mnt753_domain* d = new (std::nothrow) mnt753_domain();
+  if (!d) return set_error(MNT753_ENOMEM, "domain_create_for: host allocation failed");
+  d->curve = curve; d->frm = frm; d->m = m; d->kind = kind;
+  d->big_m = kind == MNT753_DOMAIN_STEP ? (size_t)1 << (ceil_log2(m) - 1) : m / 2;
+  d->small_m = m - d->big_m;
+  d->device = current_physical_device(); d->logical_device = mnt753_get_device();
+  OnDevice on(d->device);
+  int rc = create_basic(curve, frm, d->big_m, true, &d->sub_big);
+  if (!rc) {
+    if (kind == MNT753_DOMAIN_EXTENDED) d->sub_small = d->sub_big;      // both halves are size-small_m transforms, one after the other
+    else if (d->small_m > 1) rc = create_basic(curve, frm, d->small_m, true, &d->sub_small);
+  }
+  if (!rc) rc = frm == MOD_A ? build_outer<MOD_A>(d) : build_outer<MOD_B>(d);
+  if (rc) { mnt753_domain_free(d); return rc; }
+  *out = d;
+  return 0;
+}
+
+// ---- which domain libfqfft's get_evaluation_domain(min_size) builds (get_evaluation_domain.tcc:58-135) -----------------------------
+// Each candidate is accepted by its constructor's own test.  MNT6753's Fr has a small subgroup of order 5^2 defined
+// (mnt6753_init.cpp:73-75): there basic_radix2_domain accepts every 2^a 5^b, a <= 15, b <= 2, and get_root_of_unity likewise.
+// A candidate the reference accepts and this library does not build ends the walk with MNT753_EDOMAIN.
+struct Pick { int kind; size_t m; };           // kind < 0: refused, the message is set
+constexpr int Q_BASE = 5, Q_POWER = 2;         // MNT6753 Fr: small_subgroup_base, small_subgroup_power
+bool small_subgroup(int frm) { return frm == MOD_B; }
+void split_2q(size_t n, int& a, int& b, size_t& rest) {
+  a = b = 0;
+  while (n % 2 == 0) { n /= 2; ++a; }
+  while (n % Q_BASE == 0) { n /= Q_BASE; ++b; }
+  rest = n;
+}
+// libff get_root_of_unity(n) succeeds (field_utils.tcc:40-89)
+bool has_root(int frm, size_t n) {
+  if (n == 0) return false;
+  if (small_subgroup(frm)) {
+    int a, b; size_t rest;
+    split_2q(n, a, b, rest);
+    return rest == 1 && a <= FRD[frm].two_adicity && b <= Q_POWER;
+  }
+  return is_pow2(n) && ceil_log2(n) <= FRD[frm].two_adicity;
+}
+bool basic_accepts(int frm, size_t m) {        // basic_radix2_domain.tcc:26-60
+  if (m <= 1) return false;
+  if (small_subgroup(frm)) {
+    int a, b; size_t rest;
+    split_2q(m, a, b, rest);
+    return rest == 1 && has_root(frm, m);
+  }
+  return ceil_log2(m) <= FRD[frm].two_adicity && has_root(frm, m);
+}
+bool extended_accepts(int frm, size_t m) {     // extended_radix2_domain.tcc:21-46
+  return m > 1 && ceil_log2(m) == FRD[frm].two_adicity + 1 && has_root(frm, m / 2);
+}
+bool step_accepts(int frm, size_t m) {         // step_radix2_domain.tcc:21-53
+  if (m <= 1) return false;
+  const int l = ceil_log2(m);
+  if (l >= 63) return false;
+  const size_t big_m = (size_t)1 << (l - 1), small_m = m - big_m;
+  return is_pow2(small_m) && has_root(frm, (size_t)1 << l) && has_root(frm, small_m);
+}
+Pick refuse(const char* curve_name, size_t min_size, const char* fmt, size_t a) {
+  char what[160], msg[320];
+  snprintf(what, sizeof what, fmt, a);
+  snprintf(msg, sizeof msg, "domain_create_for: %s, min_size %zu: the reference uses %s, which this library does not build", curve_name, min_size, what);
+  set_error(MNT753_EDOMAIN, msg);
+  return Pick{-1, 0};
+}
+Pick select_domain(int frm, size_t min_size) {
+  const char* name = frm == MOD_A ? "MNT4753" : "MNT6753";
+  if (min_size <= 1) {
+    set_error(MNT753_EDOMAIN, "domain_create_for: min_size must be above 1 (no domain of the reference accepts 0 or 1)");
+    return Pick{-1, 0};
+  }
+  if (ceil_log2(min_size) >= 62) return refuse(name, min_size, "no radix-2 domain (size %zu is beyond every root of unity)", min_size);
+  const size_t big = (size_t)1 << (ceil_log2(min_size) - 1), small = min_size - big;
+  const size_t sizes[2] = {min_size, big + ((size_t)1 << ceil_log2(small))};
+  for (int pass = 0; pass < 2; ++pass) {       // candidates 1-3 at min_size, 4-6 at big + rounded_small
+    const size_t m = sizes[pass];
+    if (basic_accepts(frm, m)) {
+      if (is_pow2(m)) return Pick{MNT753_DOMAIN_BASIC, m};
+      return refuse(name, min_size, "a mixed-radix basic_radix2_domain of size %zu (2^a 5^b)", m);
+    }
+    if (extended_accepts(frm, m)) {
+      if (m % 2 == 0 && is_pow2(m / 2)) return Pick{MNT753_DOMAIN_EXTENDED, m};
+      return refuse(name, min_size, "an extended_radix2_domain of size %zu over a mixed-radix half", m);
+    }
+    if (step_accepts(frm, m)) return Pick{MNT753_DOMAIN_STEP, m};      // big_m and small_m are powers of two: plain radix 2
+  }
+  if (small_subgroup(frm)) {                   // candidate 7: the smallest 2^a 5^b >= min_size, a <= s, b <= 2
+    size_t best = SIZE_MAX;
+    for (int b = 0; b <= Q_POWER; ++b) {
+      size_t r = 1;
+      for (int i = 0; i < b; ++i) r *= Q_BASE;
+      int a = 0;
+      while (r < min_size) { r *= 2; ++a; }
+      if (a <= FRD[frm].two_adicity && r < best) best = r;
+    }
+    if (best != SIZE_MAX && basic_accepts(frm, best)) {
+      if (is_pow2(best)) return Pick{MNT753_DOMAIN_BASIC, best};
+      return refuse(name, min_size, "a mixed-radix basic_radix2_domain of size %zu (2^a 5^b, candidate 7)", best);
+    }
+  }
+  return refuse(name, min_size, "a geometric or arithmetic sequence domain of size %zu (past candidate 7)", min_size);
 }
 
 }  // namespace
@@ -175,21 +484,28 @@ int mnt753_domain_create(int curve, size_t m, mnt753_domain** out) {
   while (((size_t)1 << logm) < m) ++logm;
   if (m <= 1 || ((size_t)1 << logm) != m || logm > FRD[frm].two_adicity)
     return set_error(MNT753_EDOMAIN, "domain_create: size must be a power of two in (1, 2^s], s = 30 (MNT4753) / 15 (MNT6753)");
-  mnt753_domain* d = new (std::nothrow) mnt753_domain();
-  if (!d) return set_error(MNT753_ENOMEM, "domain_create: host allocation failed");
-  d->curve = curve; d->frm = frm; d->m = m; d->logm = logm;
-  d->device = current_physical_device(); d->logical_device = mnt753_get_device();
-  OnDevice on(d->device);
-  int rc = frm == MOD_A ? build_tables<MOD_A>(d) : build_tables<MOD_B>(d);
-  if (rc) { mnt753_domain_free(d); return rc; }
-  *out = d;
-  return 0;
+  return create_basic(curve, frm, m, false, out);
 }
+
+int mnt753_domain_create_for(int curve, size_t min_size, mnt753_domain** out) {
+  if (!out || curve < 0 || curve > 1) return set_error(MNT753_EINVAL, "domain_create_for: bad argument");
+  if (int rc = require_device()) return rc;
+  const int frm = curve == MNT753_CURVE_MNT4753 ? MOD_A : MOD_B;
+  const Pick p = select_domain(frm, min_size);
+  if (p.kind < 0) return MNT753_EDOMAIN;
+  if (p.kind == MNT753_DOMAIN_BASIC) return create_basic(curve, frm, p.m, false, out);
+  return create_outer(curve, frm, p.kind, p.m, out);
+}
+
+int mnt753_domain_kind(const mnt753_domain* d) { return d ? d->kind : -1; }
 
 int mnt753_domain_free(mnt753_domain* d) {
   if (!d) return 0;
+  if (d->sub_small && d->sub_small != d->sub_big) mnt753_domain_free(d->sub_small);
+  if (d->sub_big) mnt753_domain_free(d->sub_big);
   OnDevice on(d->device);
-  void* ptrs[] = {d->tw_fwd, d->tw_inv, d->cos_fwd, d->cos_fwd_s, d->cos_inv_s, d->consts, d->work, d->stage};
+  void* ptrs[] = {d->tw_fwd, d->tw_inv, d->cos_fwd, d->cos_fwd_s, d->cos_inv_s, d->consts, d->work, d->stage,
+                  d->x_fwd, d->x_inv, d->x_inv2, d->xcos_fwd, d->xcos_inv, d->xconsts, d->zt, d->zt12};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (d->work_free) (void)hipEventDestroy(d->work_free);
   delete d;
@@ -229,7 +545,10 @@ int mnt753_divide_by_z_on_coset(mnt753_domain* d, uint64_t* dev_vec, void* strea
   const unsigned gb = (unsigned)((d->m + 255) / 256);
   uint32_t* v = reinterpret_cast<uint32_t*>(dev_vec);
   OnDevice on(d->device);
-  if (d->frm == MOD_A) hipLaunchKernelGGL((k_vec_mul_const<MOD_A>), dim3(gb), dim3(256), 0, (hipStream_t)stream, v, d->consts + 3 * FPS_WORDS, d->m);
+  if (d->kind != MNT753_DOMAIN_BASIC) {
+    if (d->frm == MOD_A) hipLaunchKernelGGL((k_vec_mul_ztab<MOD_A>), dim3(gb), dim3(256), 0, (hipStream_t)stream, v, d->zt, d->z_split, d->z_mask, d->m);
+    else hipLaunchKernelGGL((k_vec_mul_ztab<MOD_B>), dim3(gb), dim3(256), 0, (hipStream_t)stream, v, d->zt, d->z_split, d->z_mask, d->m);
+  } else if (d->frm == MOD_A) hipLaunchKernelGGL((k_vec_mul_const<MOD_A>), dim3(gb), dim3(256), 0, (hipStream_t)stream, v, d->consts + 3 * FPS_WORDS, d->m);
   else hipLaunchKernelGGL((k_vec_mul_const<MOD_B>), dim3(gb), dim3(256), 0, (hipStream_t)stream, v, d->consts + 3 * FPS_WORDS, d->m);
   HIP_TRY(hipGetLastError());
   return 0;

@@ -312,6 +312,228 @@ __global__ void k_consts_to_internal(uint32_t* __restrict__ out, const uint32_t*
   fp_store(out + i * FPS_WORDS, v);
 }
 
+// ---- step and extended radix-2 domains (libfqfft step_radix2_domain.tcc, extended_radix2_domain.tcc) ---------------------------
+// A domain of size big_m + small_m (step) or 2 * small_m (extended) is two radix-2 transforms (k_ntt_group, unchanged) with one
+// O(m) pass in front of them (forward) or behind them (inverse).  The passes are out of place -- vec -> work in front, work -> vec
+// behind -- so the inner transforms read one buffer and write the other and no pass needs a copy.  Wire in, wire out; tables in
+// device form; one element (pair) per lane.  COSET multiplies by g^k on the way in (forward) / g^-k on the way out (inverse), the
+// _multiply_by_coset of cosetFFT / icosetFFT.
+
+template <int M>
+__device__ __forceinline__ void load_wire_fp(Fp<M>& x, const uint32_t* p) {
+  uint32_t w[24];
+  load_wire24(w, p);
+  fp_unpack(x, w);
+}
+template <int M>
+__device__ __forceinline__ void store_wire_fp(uint32_t* p, const Fp<M>& x) {
+  Fp<M> c;
+  uint32_t w[24];
+  fp_canon(c, x);
+  fp_pack(w, c);
+  store_wire24(p, w);
+}
+template <int M>
+__device__ __forceinline__ void mul_table(Fp<M>& x, const uint32_t* entry) {
+  Fp<M> k, y;
+  fp_load(k, entry);
+  fp_mul(y, x, k);
+  x = y;
+}
+
+// Step, forward:  out[k] = c[k] = a[k] (+ a[k + big_m] for k < small_m),  k < big_m
+//                 out[big_m + i] = e[i] = sum_j d[i + j small_m],  d[k] = omega^k (a[k] (- a[k + big_m] for k < small_m))
+// Mapping: a block is ti_n x tj_n threads; thread (ti, tj) of block b owns output i = b ti_n + ti and walks j = tj, tj + tj_n, ...
+// ti is the fast index, so the lanes of a wave read consecutive elements k = i + j small_m for every j (and where small_m < 64,
+// k = threadIdx.x itself): each load of the strided fold is coalesced.  The tj_n partial sums of one output meet in LDS.
+// The host picks ti_n = min(small_m, 64), tj_n = min(compr, 256 / ti_n); both powers of two, ti_n divides small_m.
+template <int M, bool COSET>
+__global__ void __launch_bounds__(256) k_step_pre(const uint32_t* __restrict__ a, uint32_t* __restrict__ out,
+                                                 const uint32_t* __restrict__ om, const uint32_t* __restrict__ cos,
+                                                 size_t big_m, size_t small_m, int ti_n, int tj_n) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[256 * FPS_WORDS];
+  const int ti = threadIdx.x % ti_n, tj = threadIdx.x / ti_n;
+  const size_t i = (size_t)blockIdx.x * ti_n + ti;            // < small_m: ti_n divides small_m
+  const size_t compr = big_m / small_m;
+  Fp<M> acc;
+  fp_zero(acc);
+#pragma unroll 1
+  for (size_t j = tj; j < compr; j += tj_n) {
+    const size_t k = i + j * small_m;
+    Fp<M> x, c, dd;
+    load_wire_fp(x, a + k * 24);
+    if constexpr (COSET) mul_table(x, cos + k * FPS_WORDS);
+    if (j == 0) {
+      Fp<M> y;
+      load_wire_fp(y, a + (k + big_m) * 24);
+      if constexpr (COSET) mul_table(y, cos + (k + big_m) * FPS_WORDS);
+      fp_add(c, x, y);
+      fp_sub(dd, x, y);
+    } else {
+      c = x;
+      dd = x;
+    }
+    store_wire_fp(out + k * 24, c);
+    mul_table(dd, om + k * FPS_WORDS);
+    fp_add(c, acc, dd);
+    acc = c;
+  }
+  lds_store_fp(lds + threadIdx.x * FPS_WORDS, acc);
+  __syncthreads();
+  if (tj == 0) {
+#pragma unroll 1
+    for (int q = 1; q < tj_n; ++q) {
+      Fp<M> t, s;
+      lds_load_fp(t, lds + (q * ti_n + ti) * FPS_WORDS);
+      fp_add(s, acc, t);
+      acc = s;
+    }
+    store_wire_fp(out + (big_m + i) * 24, acc);
+  }
+}
+
+// Step, inverse, behind the two inverse transforms (w = their raw outputs):
+//   U0[k] = w[k] / big_m;  a[k] = U0[k] for k >= small_m
+//   U1[i] = (w[big_m + i] / small_m - sum_{j >= 1} omega^k U0[k]) omega^-i,  k = i + j small_m
+//   a[i] = (U0[i] + U1[i]) / 2;  a[big_m + i] = (U0[i] - U1[i]) / 2
+// The halves ride in the tables: om_s[k] = omega^k / (2 big_m), om_inv[i] = omega^-i, kc = {1 / (2 big_m), 1 / (2 small_m), 1 / big_m}.
+// Same thread mapping as k_step_pre.
+template <int M, bool COSET>
+__global__ void __launch_bounds__(256) k_step_post(const uint32_t* __restrict__ w, uint32_t* __restrict__ a,
+                                                  const uint32_t* __restrict__ om_s, const uint32_t* __restrict__ om_inv,
+                                                  const uint32_t* __restrict__ cos_inv, const uint32_t* __restrict__ kc,
+                                                  size_t big_m, size_t small_m, int ti_n, int tj_n) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[256 * FPS_WORDS];
+  const int ti = threadIdx.x % ti_n, tj = threadIdx.x / ti_n;
+  const size_t i = (size_t)blockIdx.x * ti_n + ti;
+  const size_t compr = big_m / small_m;
+  Fp<M> acc, u0h;
+  fp_zero(acc);
+  fp_zero(u0h);
+#pragma unroll 1
+  for (size_t j = tj; j < compr; j += tj_n) {
+    const size_t k = i + j * small_m;
+    Fp<M> x;
+    load_wire_fp(x, w + k * 24);
+    if (j == 0) {
+      u0h = x;
+      mul_table(u0h, kc);
+    } else {
+      Fp<M> t = x, s;
+      mul_table(t, om_s + k * FPS_WORDS);
+      fp_add(s, acc, t);
+      acc = s;
+      mul_table(x, kc + 2 * FPS_WORDS);
+      if constexpr (COSET) mul_table(x, cos_inv + k * FPS_WORDS);
+      store_wire_fp(a + k * 24, x);
+    }
+  }
+  lds_store_fp(lds + threadIdx.x * FPS_WORDS, acc);
+  __syncthreads();
+  if (tj == 0) {        // this thread took j = 0: u0h is set
+#pragma unroll 1
+    for (int q = 1; q < tj_n; ++q) {
+      Fp<M> t, s;
+      lds_load_fp(t, lds + (q * ti_n + ti) * FPS_WORDS);
+      fp_add(s, acc, t);
+      acc = s;
+    }
+    Fp<M> y, u1h, lo, hi;
+    load_wire_fp(y, w + (big_m + i) * 24);
+    mul_table(y, kc + 1 * FPS_WORDS);
+    fp_sub(u1h, y, acc);
+    mul_table(u1h, om_inv + i * FPS_WORDS);
+    fp_add(lo, u0h, u1h);
+    fp_sub(hi, u0h, u1h);
+    if constexpr (COSET) {
+      mul_table(lo, cos_inv + i * FPS_WORDS);
+      mul_table(hi, cos_inv + (big_m + i) * FPS_WORDS);
+    }
+    store_wire_fp(a + i * 24, lo);
+    store_wire_fp(a + (big_m + i) * 24, hi);
+  }
+}
+
+// Extended, forward:  out[i] = a[i] + a[s + i];  out[s + i] = shift^i (a[i] + shift^s a[s + i]),  s = small_m.   kc = {shift^s}
+template <int M, bool COSET>
+__global__ void __launch_bounds__(256) k_ext_pre(const uint32_t* __restrict__ a, uint32_t* __restrict__ out,
+                                                const uint32_t* __restrict__ sh, const uint32_t* __restrict__ cos,
+                                                const uint32_t* __restrict__ kc, size_t small_m) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= small_m) return;
+  Fp<M> x, y, s, t;
+  load_wire_fp(x, a + i * 24);
+  load_wire_fp(y, a + (small_m + i) * 24);
+  if constexpr (COSET) {
+    mul_table(x, cos + i * FPS_WORDS);
+    mul_table(y, cos + (small_m + i) * FPS_WORDS);
+  }
+  fp_add(s, x, y);
+  store_wire_fp(out + i * 24, s);
+  mul_table(y, kc);
+  fp_add(t, x, y);
+  mul_table(t, sh + i * FPS_WORDS);
+  store_wire_fp(out + (small_m + i) * 24, t);
+}
+
+// Extended, inverse, behind the two inverse transforms (w0 = w[0, s), w1 = w[s, 2s)):
+//   a[i] = sconst (shift^-i w1[i] - shift^s w0[i]);  a[s + i] = sconst (w0[i] - shift^-i w1[i])
+// sh_inv_s[i] = sconst shift^-i;  kc = {shift^s, sconst},  sconst = 1 / (s (1 - shift^s))
+template <int M, bool COSET>
+__global__ void __launch_bounds__(256) k_ext_post(const uint32_t* __restrict__ w, uint32_t* __restrict__ a,
+                                                 const uint32_t* __restrict__ sh_inv_s, const uint32_t* __restrict__ cos_inv,
+                                                 const uint32_t* __restrict__ kc, size_t small_m) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= small_m) return;
+  Fp<M> u, t, lo, hi;
+  load_wire_fp(u, w + i * 24);
+  load_wire_fp(t, w + (small_m + i) * 24);
+  mul_table(u, kc + 1 * FPS_WORDS);
+  mul_table(t, sh_inv_s + i * FPS_WORDS);
+  fp_sub(hi, u, t);
+  mul_table(u, kc);
+  fp_sub(lo, t, u);
+  if constexpr (COSET) {
+    mul_table(lo, cos_inv + i * FPS_WORDS);
+    mul_table(hi, cos_inv + (small_m + i) * FPS_WORDS);
+  }
+  store_wire_fp(a + i * 24, lo);
+  store_wire_fp(a + (small_m + i) * 24, hi);
+}
+
+// 1 / Z on the coset takes few distinct values on these domains: entry (i & mask) of `zt` for i < split, entry mask + 1 behind it.
+//   step:      split = big_m, mask = compr - 1 (omega^(2 small_m) has order compr = big_m / small_m);   extended: split = small_m, mask = 0
+__device__ __forceinline__ size_t z_index(size_t i, size_t split, size_t mask) { return i < split ? (i & mask) : mask + 1; }
+
+// a[i] = a[i] / Z(g x_i)       (divide_by_Z_on_coset; zt in device form)
+template <int M>
+__global__ void __launch_bounds__(256) k_vec_mul_ztab(uint32_t* __restrict__ a, const uint32_t* __restrict__ zt, size_t split, size_t mask, size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Fp<M> x;
+  load_wire_fp(x, a + i * 24);
+  mul_table(x, zt + z_index(i, split, mask) * FPS_WORDS);
+  store_wire_fp(a + i * 24, x);
+}
+
+// k_h_pointwise with 1 / Z from the table:  k2t[.] = Z^-1 * R' * 2^-12
+template <int M>
+__global__ void __launch_bounds__(256) k_h_pointwise_ztab(uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                         const uint32_t* __restrict__ cvec, const uint32_t* __restrict__ k1,
+                                                         const uint32_t* __restrict__ k2t, size_t split, size_t mask, size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Fp<M> x, y, z, ab, d;
+  load_wire_fp(x, a + i * 24);
+  load_wire_fp(y, b + i * 24);
+  load_wire_fp(z, cvec + i * 24);
+  fp_mul(ab, x, y);
+  mul_table(z, k1);
+  fp_sub(d, ab, z);
+  mul_table(d, k2t + z_index(i, split, mask) * FPS_WORDS);
+  store_wire_fp(a + i * 24, d);
+}
+
 static __global__ void __launch_bounds__(256) k_copy_h(uint32_t* __restrict__ h, const uint32_t* __restrict__ a, size_t m) {
   // h[0..m) = a[0..m), h[m] = 0      (vector_Fr_zeros(m+1) + vector_Fr_copy_into, cuda_prover_piecewise.cu:50-51)
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // one thread per 16-byte quad

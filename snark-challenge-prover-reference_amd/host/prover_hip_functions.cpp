@@ -682,7 +682,8 @@ template <int CURVE> void HIP_B::print_G2(G2* a) {
   }
 }
 
-// Domains (twiddle and coset tables, ~0.5 GB of HBM at 2^20) are cached per (curve, size): creating one allocates and
+// Domains (twiddle and coset tables, ~0.5 GB of HBM at 2^20; basic, extended or step radix-2 as libfqfft's get_evaluation_domain
+// chooses) are cached per (curve, size): creating one allocates and
 // frees device memory, which synchronises the whole device and would stall behind MSMs already in flight.  read_params
 // creates the domain for d + 1 ahead of time -- it depends on the parameters only, like the MSM window tables.
 template <int CURVE> static std::shared_ptr<DomainHolder> cached_domain(size_t d, int device = 0) {
@@ -694,8 +695,13 @@ template <int CURVE> static std::shared_ptr<DomainHolder> cached_domain(size_t d
   auto h = std::make_shared<DomainHolder>();
   {
     DeviceScope on(device);   // a domain lives on the device that is current when it is created
-    check(mnt753_domain_create(CURVE, d, &h->h), "mnt753_domain_create");
+    check(mnt753_domain_create_for(CURVE, d, &h->h), "mnt753_domain_create_for");
   }
+  // libfqfft's get_evaluation_domain may round a size up (big + rounded_small).  The reference prover then throws from iFFT, whose
+  // vectors have d + 1 elements and not m: no proof exists for such parameters, and none is written here either
+  if (const size_t m = mnt753_domain_size(h->h); m != d)
+    throw std::runtime_error("the evaluation domain for d + 1 = " + std::to_string(d) + " has " + std::to_string(m) +
+                             " elements: the reference's iFFT refuses vectors of another size than the domain's (a.size() != m), there is no proof for these parameters");
   cache[{device, d}] = h;
   return h;
 }

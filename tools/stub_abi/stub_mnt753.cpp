@@ -142,6 +142,13 @@ int mnt753_domain_create(int curve, size_t m, mnt753_domain** out) {
   if (!out || curve < 0 || curve > 1 || m == 0 || (m & (m - 1))) return fail(MNT753_EDOMAIN, "domain_create: not a power of two");
   *out = new mnt753_domain{curve, m, t_dev}; return 0;
 }
+// (the stub has no arithmetic: any size above 1 is taken as it is, which is all the wrapper's plumbing needs)
+int mnt753_domain_create_for(int curve, size_t min_size, mnt753_domain** out) {
+  if (!out || curve < 0 || curve > 1) return fail(MNT753_EINVAL, "domain_create_for: bad argument");
+  if (min_size <= 1) return fail(MNT753_EDOMAIN, "domain_create_for: min_size must be above 1");
+  *out = new mnt753_domain{curve, min_size, t_dev}; return 0;
+}
+int mnt753_domain_kind(const mnt753_domain* d) { return !d ? -1 : (d->m & (d->m - 1)) ? MNT753_DOMAIN_STEP : MNT753_DOMAIN_BASIC; }
 int mnt753_domain_free(mnt753_domain* d) { delete d; return 0; }
 size_t mnt753_domain_size(const mnt753_domain* d) { return d ? d->m : 0; }
 static void touch(uint64_t* v, size_t n) { volatile uint64_t s = 0; for (size_t i = 0; i < 12 * n; i += 12) { s += v[i]; v[i] = v[i]; } (void)s; }

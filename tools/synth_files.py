@@ -14,7 +14,12 @@ DEFAULT_SEED = 0x6d696e61   # SURVEY.md section 8d; tests/golden/oracle_hashes.j
 
 
 def write_files(pkg, curve, log2_d, params_path, input_path, seed=DEFAULT_SEED):
-    d = (1 << log2_d) - 1
+    return write_files_d(pkg, curve, (1 << log2_d) - 1, params_path, input_path, seed)
+
+
+def write_files_d(pkg, curve, d, params_path, input_path, seed=DEFAULT_SEED):
+    """the same files for any degree d (the evaluation domain is get_evaluation_domain(d + 1): extended and step radix-2 sizes as well
+    as powers of two); same seeds and layout, m = d + 1"""
     m = d + 1
     with open(params_path, "wb") as f:
         np.array([d, m], dtype=np.uint64).tofile(f)
