@@ -261,6 +261,35 @@ size_t mnt753_r1cs_num_variables(const mnt753_r1cs* r); /* m: dev_w of mnt753_r1
 size_t mnt753_r1cs_num_inputs(const mnt753_r1cs* r);
 int mnt753_r1cs_evaluate(mnt753_r1cs* r, const uint64_t* dev_w, uint64_t* dev_ca, uint64_t* dev_cb, uint64_t* dev_cc, size_t out_len, void* stream);
 
+/* ---- input validation (device) --------------------------------------------------------------------------
+ * The reference prover trusts its files (unchecked fread, prover_reference_functions.cpp:48-116); what the reference HAS for the
+ * purpose is libff's G::is_well_formed() (depends/libff/libff/algebra/curves/mnt753/mnt4753/mnt4753_g1.cpp:348, mnt4753_g2.cpp:371-396,
+ * mnt6753_g1.cpp:348, mnt6753_g2.cpp:377: the curve equation) and r1cs_constraint_system::is_satisfied, asserted before a witness is
+ * mapped (libsnark/reductions/r1cs_to_qap/r1cs_to_qap.tcc:216).  These calls are those checks on wire-format words, on the device
+ * (csrc/mnt753_validate.hip).  A malformed input is a RESULT, not a failed call: they return 0 and fill *out (host memory; the call
+ * blocks until it is filled) with the number of bad elements, the lowest bad index and that index's reason -- the same record
+ * whatever the scheduling.  n = 0 gives an all-zero report.  Null pointers / bad ids: MNT753_EINVAL; no device: MNT753_ENODEV.
+ * MNT753_EINPUT is what the wrapper classes and main_hip make of a report with n_bad > 0 (main_hip: exit code 3). */
+#define MNT753_EINPUT (-7)            /* an input failed validation (wrapper / CLI level; the check calls themselves return 0) */
+enum { MNT753_BAD_NONE = 0, MNT753_BAD_NONCANONICAL = 1, MNT753_BAD_OFF_CURVE = 2, MNT753_BAD_UNSATISFIED = 3 };
+typedef struct { uint64_t n_bad, first_bad; uint32_t first_reason, reserved; } mnt753_check_report;
+/* n affine points in the wire format (on_device != 0: a device pointer).  Per point, the first that applies: a coordinate component
+ * >= q -> MNT753_BAD_NONCANONICAL; all words of y zero -> the identity as read_g1 / read_g2 decode it (serialization.hpp:84-111),
+ * well formed whatever x holds; y^2 != x^3 + a x + b (G2: the twist's a', b', mnt4753_init.cpp:122-123, mnt6753_init.cpp:133-136) ->
+ * MNT753_BAD_OFF_CURVE.  is_well_formed() of the four groups; like it, no subgroup test for G2. */
+int mnt753_check_points(int curve, int group, const uint64_t* affine, int on_device, size_t n, mnt753_check_report* out, void* stream);
+/* n Fr elements of the curve: bad = the stored integer is >= r (MNT753_BAD_NONCANONICAL).  The field layer's contracts start from
+ * canonical words (libff's Fp_model keeps them so, fp.tcc:161-186; a file can hold anything). */
+int mnt753_check_scalars(int curve, const uint64_t* fr, int on_device, size_t n, mnt753_check_report* out, void* stream);
+/* a[i] b[i] == c[i] in Fr for i < n on three device vectors: over the d + 1 entries of ca / cb / cc this is
+ * r1cs_constraint_system::is_satisfied (r1cs.tcc: <a_i, w> <b_i, w> = <c_i, w> per constraint; the input-consistency rows hold
+ * (w_i, 0, 0) and pass).  Right for any words: a row with an operand >= r is MNT753_BAD_NONCANONICAL, else a failing product is
+ * MNT753_BAD_UNSATISFIED. */
+int mnt753_check_products(int curve, const uint64_t* dev_a, const uint64_t* dev_b, const uint64_t* dev_c, size_t n, mnt753_check_report* out, void* stream);
+/* cs.is_satisfied(primary_input, auxiliary_input) (r1cs_to_qap.tcc:216) for the assignment dev_w (m + 1 elements, w[0] = 1):
+ * mnt753_r1cs_evaluate into scratch vectors, then mnt753_check_products; first_bad = the lowest unsatisfied constraint row. */
+int mnt753_r1cs_check(mnt753_r1cs* r, const uint64_t* dev_w, mnt753_check_report* out, void* stream);
+
 /* ---- uniform scalars (host) ---------------------------------------------------------------------------
  * n elements of Fr of the curve, uniform in [0, r) by rejection on 753-bit draws of a seeded SplitMix64, in wire form.  What the
  * product needs them for: the scalars of the warm-up MSMs at parameter-load time (B::read_params) and the prover's second random

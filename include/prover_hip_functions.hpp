@@ -129,6 +129,30 @@ public:
   static r1cs *read_r1cs(const char *path);
   static groth16_input *read_witness(const char *path, groth16_params *params, r1cs *cs);
   static void delete_r1cs(r1cs *a);
+  // Input validation on the device (include/mnt753_hip.h, "input validation"; the reference's counterparts are libff's
+  // G::is_well_formed() and the cs.is_satisfied() assertion of r1cs_to_qap.tcc:216 -- its prover wrapper has neither).  One entry per
+  // set that was looked at: its name (A, B1, B2, L, H; w, ca, cb, cc, r; "constraints" for the rows ca[i] cb[i] = cc[i]), its size,
+  // the number of bad elements, the lowest bad index inside the set (file order, also with several devices) and that index's reason
+  // (MNT753_BAD_*).  Nothing throws for a malformed input; I/O and device errors throw as everywhere.
+  struct check_entry { const char *set; size_t size; uint64_t n_bad, first_bad; int reason; };
+  struct check_report {
+    check_entry sets[8];
+    int n_sets = 0;
+    bool ok() const { for (int k = 0; k < n_sets; ++k) if (sets[k].n_bad) return false; return true; }
+    const check_entry *first_bad() const { for (int k = 0; k < n_sets; ++k) if (sets[k].n_bad) return &sets[k]; return nullptr; }
+  };
+  // check_params: the five point sets of the file the parameters were read from -- the base sets keep their points in the device
+  // radix, so the wire points are streamed from the file once more (every device its own slices, mnt753_load_file_to_device) into a
+  // block that lives for the check only.  check_input: w, ca, cb, cc, r canonical, and ca[i] cb[i] = cc[i] for every row -- call it
+  // before compute_H, which overwrites the three vectors; it waits for the input's loaders.
+  static check_report check_params(groth16_params *params);
+  static check_report check_input(groth16_input *input, groth16_params *params);
+  // the same from files alone: no base sets, no window tables, no evaluation domain (what `main_hip <curve> check` runs);
+  // input_path may be null.  check_witness_file: w and r canonical, and mnt753_r1cs_check of w against the system.
+  static check_report check_params_file(const char *params_path);
+  static check_report check_input_file(const char *params_path, const char *input_path);
+  static check_report check_witness_file(const char *params_path, r1cs *cs, const char *witness_path);
+  static const char *check_reason_text(int reason);
   // seconds the background loader of read_input needed until the whole input file was on the device (waits for it)
   static double input_load_seconds(groth16_input *input);
   // raw access for tests / tools

@@ -17,6 +17,14 @@ class Mnt753Error(RuntimeError):
     pass
 
 
+BAD_NONE, BAD_NONCANONICAL, BAD_OFF_CURVE, BAD_UNSATISFIED = 0, 1, 2, 3
+
+
+class CheckReport(C.Structure):
+    """mnt753_check_report"""
+    _fields_ = [("n_bad", C.c_uint64), ("first_bad", C.c_uint64), ("first_reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 def lib_path():
     """The product library next to this file; MNT753_LIB names another build of it (development A/B runs: an experimental
     variant is loaded from where it was built instead of being copied over the product file)."""
@@ -98,6 +106,10 @@ def lib():
         "mnt753_r1cs_num_variables": (sz, [vp]),
         "mnt753_r1cs_num_inputs": (sz, [vp]),
         "mnt753_r1cs_evaluate": (i, [vp, vp, vp, vp, vp, sz, vp]),
+        "mnt753_check_points": (i, [i, i, vp, i, sz, C.POINTER(CheckReport), vp]),
+        "mnt753_check_scalars": (i, [i, vp, i, sz, C.POINTER(CheckReport), vp]),
+        "mnt753_check_products": (i, [i, vp, vp, vp, sz, C.POINTER(CheckReport), vp]),
+        "mnt753_r1cs_check": (i, [vp, vp, C.POINTER(CheckReport), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)   # AttributeError here = the library does not export what the header declares
@@ -422,6 +434,46 @@ def synth_expected_msm(curve, group, seed, scalars):
     return out
 
 
+def _input_ptr(data, on_device, words, n):
+    """-> (pointer, element count, array to keep alive) for a numpy array or, with on_device, a device address"""
+    if on_device:
+        return C.c_void_p(int(data)), int(n), None
+    keep = np.ascontiguousarray(data, dtype=np.uint64)
+    return C.c_void_p(keep.ctypes.data), (keep.size // words if n is None else int(n)), keep
+
+
+def _report(rep):
+    return int(rep.n_bad), int(rep.first_bad), int(rep.first_reason)
+
+
+def check_points(curve, group, affine, on_device=False, n=None, stream=None):
+    """mnt753_check_points: canonical coordinates and the curve equation for n affine wire points (a numpy array, or a device address
+    with on_device) -> (n_bad, first_bad, reason of first_bad: BAD_*)."""
+    ptr, cnt, keep = _input_ptr(affine, on_device, affine_words(curve, group), n)
+    rep = CheckReport()
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    _check(lib().mnt753_check_points(curve, group, ptr, 1 if on_device else 0, cnt, C.byref(rep), st), "mnt753_check_points")
+    return _report(rep)
+
+
+def check_scalars(curve, fr, on_device=False, n=None, stream=None):
+    """mnt753_check_scalars: every Fr element below r -> (n_bad, first_bad, reason)."""
+    ptr, cnt, keep = _input_ptr(fr, on_device, 12, n)
+    rep = CheckReport()
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    _check(lib().mnt753_check_scalars(curve, ptr, 1 if on_device else 0, cnt, C.byref(rep), st), "mnt753_check_scalars")
+    return _report(rep)
+
+
+def check_products(curve, dev_a, dev_b, dev_c, n, stream=None):
+    """mnt753_check_products: a[i] b[i] == c[i] in Fr on three device vectors -> (n_bad, first_bad row, reason)."""
+    rep = CheckReport()
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    _check(lib().mnt753_check_products(curve, C.c_void_p(int(dev_a)), C.c_void_p(int(dev_b)), C.c_void_p(int(dev_c)), int(n), C.byref(rep), st),
+           "mnt753_check_products")
+    return _report(rep)
+
+
 def read_r1cs_file(path):
     """r1cs.bin of oracle/ref_groth16.cpp: u64 num_inputs, m, nc; per matrix a, b, c: u64 row_ptr[nc + 1], u32 col[nnz], Fr coeff[nnz]."""
     raw = np.fromfile(path, dtype=np.uint8)
@@ -458,6 +510,13 @@ class R1cs:
         st = C.c_void_p(int(stream)) if stream else C.c_void_p()
         _check(lib().mnt753_r1cs_evaluate(self._h, C.c_void_p(int(dev_w)), C.c_void_p(int(dev_ca)), C.c_void_p(int(dev_cb)), C.c_void_p(int(dev_cc)),
                                           int(out_len), st), "mnt753_r1cs_evaluate")
+
+    def check(self, dev_w, stream=None):
+        """mnt753_r1cs_check: does the assignment at dev_w (m + 1 elements) satisfy the system -> (n_bad, first bad constraint row, reason)."""
+        rep = CheckReport()
+        st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+        _check(lib().mnt753_r1cs_check(self._h, C.c_void_p(int(dev_w)), C.byref(rep), st), "mnt753_r1cs_check")
+        return _report(rep)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

@@ -199,4 +199,18 @@ int mnt753_r1cs_evaluate(mnt753_r1cs* r, const uint64_t* dev_w, uint64_t* dev_ca
   return 0;
 }
 
+// cs.is_satisfied (r1cs_to_qap.tcc:216): the evaluation above into scratch vectors of nc + num_inputs + 1 entries, then the row check
+// of csrc/mnt753_validate.hip on them.  The rows behind the constraints hold (w_i, 0, 0) and pass, so a bad index is a constraint row.
+int mnt753_r1cs_check(mnt753_r1cs* r, const uint64_t* dev_w, mnt753_check_report* out, void* stream) {
+  if (!r || !dev_w || !out) return set_error(MNT753_EINVAL, "r1cs_check: null argument");
+  if (int rc = require_device()) return rc;
+  const size_t n = (size_t)(r->nc + r->num_inputs + 1);
+  uint64_t* scratch = nullptr;
+  if (hipMalloc(&scratch, 3 * 96 * n) != hipSuccess) { (void)hipGetLastError(); return set_error(MNT753_ENOMEM, "r1cs_check: device allocation failed"); }
+  int rc = mnt753_r1cs_evaluate(r, dev_w, scratch, scratch + 12 * n, scratch + 24 * n, n, stream);
+  if (rc == 0) rc = mnt753_check_products(r->curve, scratch, scratch + 12 * n, scratch + 24 * n, n, out, stream);
+  (void)hipFree(scratch);
+  return rc;
+}
+
 }  // extern "C"

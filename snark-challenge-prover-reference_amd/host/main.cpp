@@ -2,6 +2,9 @@
 //            --serve: keep the parameters resident and prove further "<input> <output>" pairs read from stdin, one per line
 // ./main_hip <curve> compute-r1cs <params> <r1cs> <witness> <output> ...      (ca / cb / cc evaluated on the device from the constraint system)
 // ./main_hip <curve> complete <keys> <input|witness> <challenge_proof> <full_proof> [--s-file <Fr> | --s-seed N]
+// ./main_hip <curve> check <params> [<input>] | check-r1cs <params> <r1cs> <witness>      (validation only; exit code 3 = malformed input)
+//            --validate on compute / compute-r1cs / complete: the same checks before proving; a failing job writes nothing
+// Exit codes: 0 success, 1 device / I/O / self-test failure, 2 usage, 3 an input failed validation.
 //
 // The prover driver, same command line as the reference binaries (libsnark/main.cpp:274-293,
 // cuda_prover_piecewise.cu:100-120).  compute_H<B> and run_prover<B> keep the reference's shape -- they are
@@ -40,6 +43,28 @@ static bool g_serve = false;    // --serve: after the listed jobs, read further 
 static int g_one_shot = -1;     // -1: decided from the job list (one job, no --serve, one device: a one-proof process); --one-shot / --tables force it
 static bool g_peer_bench = false;   // --peer-bench (with --gpus N): time the peer copies the sharded prover makes, 100 MB each, before proving
 static int g_fold_rccl = -1;    // --fold rccl | host: where the partial points of a sharded multiexp meet (default: MNT753_FOLD, else host)
+
+// --validate (or MNT753_VALIDATE=1): the parameters are checked once after they are loaded (points canonical and on their curves),
+// every job's input before its proof starts (scalars canonical, ca[i] cb[i] = cc[i] on every row -- for compute-r1cs that is the
+// witness against the system).  A failing job writes no output file; the process exits 3 if anything failed validation.
+static bool g_validate = false;
+struct validation_failed : std::runtime_error { using std::runtime_error::runtime_error; };
+
+// one line per set: "A: 1048577 points ok" / "H: 3 bad, first at 524288: off curve" / "constraint 17 of 30 is not satisfied"
+template <typename B>
+static std::string check_line(const typename B::check_entry& e) {
+  const bool rows = !strcmp(e.set, "constraints");
+  const bool points = e.set[0] >= 'A' && e.set[0] <= 'Z';
+  if (!e.n_bad) return std::string(e.set) + ": " + std::to_string(e.size) + (rows ? " rows satisfied" : (points ? " points ok" : " scalars ok"));
+  if (rows && e.reason == MNT753_BAD_UNSATISFIED)
+    return "constraint " + std::to_string(e.first_bad) + " of " + std::to_string(e.size) + " is not satisfied (" + std::to_string(e.n_bad) + " in all)";
+  return std::string(e.set) + ": " + std::to_string(e.n_bad) + " bad, first at " + std::to_string(e.first_bad) + ": " + B::check_reason_text(e.reason);
+}
+template <typename B>
+static bool print_report(const typename B::check_report& rep) {
+  for (int k = 0; k < rep.n_sets; ++k) printf("%s\n", check_line<B>(rep.sets[k]).c_str());
+  return rep.ok();
+}
 
 typedef std::chrono::steady_clock clk;
 static double secs(clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); }
@@ -82,6 +107,17 @@ void prove_one(typename B::groth16_params* params, const char* input_path, const
   auto t_main = clk::now();
   // compute-r1cs: the input file holds w and r only; ca / cb / cc come from the constraint system, evaluated on the device
   auto input = cs ? B::read_witness(input_path, params, cs) : B::read_input(input_path, params);
+  if (g_validate) {
+    // before anything is enqueued on these vectors (compute_H overwrites ca, cb, cc); waits for the input's loaders
+    const auto tv = clk::now();
+    const auto rep = B::check_input(input, params);
+    if (!g_quiet) printf("validate input: %.4fs\n", secs(tv, clk::now()));
+    if (!rep.ok()) {
+      const std::string line = check_line<B>(*rep.first_bad());
+      B::delete_groth16_input(input);
+      throw validation_failed(line);
+    }
+  }
   auto t_in = clk::now();
   if (!g_quiet) printf("load inputs (started in the background): %.3fs\n", secs(t_main, t_in));
 
@@ -200,8 +236,9 @@ static void peer_bench() {
 }
 
 // jobs: (input, output) pairs; all proved against the same resident parameters
+// returns the exit code: 0, or 3 if a job (or the parameters) failed validation
 template <typename B>
-void run_prover(const char* params_path, const std::vector<std::pair<std::string, std::string>>& jobs, const char* r1cs_path = nullptr) {
+int run_prover(const char* params_path, const std::vector<std::pair<std::string, std::string>>& jobs, const char* r1cs_path = nullptr) {
   if (g_gpus > 0) B::use_devices(g_gpus);
   B::fuse_C(g_fused_c);
   if (g_fold_rccl >= 0) B::fold_over_rccl(g_fold_rccl != 0);
@@ -223,10 +260,29 @@ void run_prover(const char* params_path, const std::vector<std::pair<std::string
   typename B::r1cs* cs = r1cs_path ? B::read_r1cs(r1cs_path) : nullptr;
   auto t_params = clk::now();
   if (!g_quiet) printf("load params: %.3fs\n", secs(t0, t_params));
+  int exit_code = 0;
+  if (g_validate) {
+    const auto tv = clk::now();
+    const auto rep = B::check_params(params);
+    if (!g_quiet) printf("validate params: %.3fs\n", secs(tv, clk::now()));
+    if (!rep.ok()) {
+      // nothing can be proved against these parameters: every job fails, nothing is written
+      fprintf(stderr, "main_hip: %s: %s\n", params_path, check_line<B>(*rep.first_bad()).c_str());
+      if (cs) B::delete_r1cs(cs);
+      B::delete_groth16_params(params);
+      return 3;
+    }
+  }
   bool first = true;
   for (const auto& job : jobs) {
     if (!g_quiet && jobs.size() > 1) printf("-- proof %s -> %s\n", job.first.c_str(), job.second.c_str());
-    prove_one<B>(params, job.first.c_str(), job.second.c_str(), t0, first, cs);
+    try {
+      prove_one<B>(params, job.first.c_str(), job.second.c_str(), t0, first, cs);
+    } catch (const validation_failed& e) {
+      fprintf(stderr, "main_hip: %s: %s\n", job.first.c_str(), e.what());
+      if (jobs.size() > 1 || g_serve) printf("failed %s: %s\n", job.second.c_str(), e.what());
+      exit_code = 3;
+    }
     first = false;
   }
   if (g_serve) {
@@ -242,6 +298,10 @@ void run_prover(const char* params_path, const std::vector<std::pair<std::string
       try {
         prove_one<B>(params, in_path, out_path, t0, false, cs);
         printf("proved %s %.3f\n", out_path, secs(tj, clk::now()));
+      } catch (const validation_failed& e) {
+        fprintf(stderr, "main_hip: %s: %s\n", in_path, e.what());
+        printf("failed %s: %s\n", out_path, e.what());
+        exit_code = 3;
       } catch (const std::exception& e) {
         printf("failed %s: %s\n", out_path, e.what());
       }
@@ -250,6 +310,26 @@ void run_prover(const char* params_path, const std::vector<std::pair<std::string
   }
   if (cs) B::delete_r1cs(cs);
   B::delete_groth16_params(params);
+  return exit_code;
+}
+
+// ./main_hip <curve> check <params> [<input>]             points of A, B1, B2, L, H; scalars of the input and its rows ca cb = cc
+// ./main_hip <curve> check-r1cs <params> <r1cs> <witness>  the same for the parameters, and the witness against the constraint system
+// One line per set on stdout; exit code 0 if everything is well formed, 3 if not.  A one-shot by nature: the files are streamed to the
+// device and checked there -- no base sets, no window tables, no level buffers, no evaluation domain, no warm-up.
+template <typename B>
+int run_check(const char* params_path, const char* input_path, const char* r1cs_path) {
+  if (g_gpus > 0) B::use_devices(g_gpus);
+  B::init_public_params();
+  bool ok = print_report<B>(B::check_params_file(params_path));
+  if (r1cs_path) {
+    auto cs = B::read_r1cs(r1cs_path);
+    try { ok = print_report<B>(B::check_witness_file(params_path, cs, input_path)) && ok; } catch (...) { B::delete_r1cs(cs); throw; }
+    B::delete_r1cs(cs);
+  } else if (input_path) {
+    ok = print_report<B>(B::check_input_file(params_path, input_path)) && ok;
+  }
+  return ok ? 0 : 3;
 }
 
 // ./main_hip <curve> complete <keys> <input|witness> <challenge_proof> <full_proof> [--s-file <Fr> | --s-seed N]
@@ -305,17 +385,50 @@ static int complete_proof(int curve, const char* keys_path, const char* input_pa
   return 0;
 }
 
+// complete --validate: the points of the key file and of the challenge proof on their curves, r canonical -- on the device like every
+// check (this is the one thing `complete` then needs a GPU for).  0, or 3 with the line on stderr; nothing is written.
+static int validate_completion(int curve, const char* keys_path, const char* input_path, const char* challenge_path) {
+  ck(mnt753_init(0), "mnt753_init");
+  const size_t g1 = 24, g2 = mnt753_affine_words(curve, MNT753_G2);
+  std::vector<uint64_t> keys(3 * g1 + 2 * g2), proof(2 * g1 + g2);
+  slurp(keys_path, 0, keys.data(), keys.size() * 8);
+  slurp(challenge_path, 0, proof.data(), proof.size() * 8);
+  uint64_t r[12];
+  slurp(input_path, 96, r, 96);
+  struct Item { const char* name; int group; const uint64_t* p; size_t n; };
+  const Item items[] = {{"keys alpha_g1 | beta_g1", MNT753_G1, keys.data(), 2}, {"keys beta_g2", MNT753_G2, keys.data() + 2 * g1, 1},
+                        {"keys delta_g1", MNT753_G1, keys.data() + 2 * g1 + g2, 1}, {"keys delta_g2", MNT753_G2, keys.data() + 3 * g1 + g2, 1},
+                        {"proof A", MNT753_G1, proof.data(), 1}, {"proof B", MNT753_G2, proof.data() + g1, 1}, {"proof C", MNT753_G1, proof.data() + g1 + g2, 1}};
+  static const char* const why[] = {"ok", "not canonical", "off curve", "not satisfied"};
+  mnt753_check_report rep;
+  for (const Item& it : items) {
+    ck(mnt753_check_points(curve, it.group, it.p, 0, it.n, &rep, nullptr), "mnt753_check_points");
+    if (rep.n_bad) { fprintf(stderr, "main_hip: %s: %llu bad, first at %llu: %s\n", it.name, (unsigned long long)rep.n_bad, (unsigned long long)rep.first_bad, why[rep.first_reason & 3u]); return 3; }
+  }
+  ck(mnt753_check_scalars(curve, r, 0, 1, &rep, nullptr), "mnt753_check_scalars");
+  if (rep.n_bad) { fprintf(stderr, "main_hip: r: 1 bad, first at 0: not canonical\n"); return 3; }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   setbuf(stdout, NULL);
   if (argc >= 7 && !strcmp(argv[2], "complete")) {
     const int curve = !strcmp(argv[1], "MNT4753") ? 0 : (!strcmp(argv[1], "MNT6753") ? 1 : -1);
     if (curve < 0) { fprintf(stderr, "unknown curve %s\n", argv[1]); return 2; }
     const char* s_file = nullptr; uint64_t s_seed = 0x73656564ull;
-    for (int i = 7; i + 1 < argc; i += 2) {
+    bool validate = false;
+    if (const char* e = getenv("MNT753_VALIDATE")) validate = atoi(e) != 0;
+    for (int i = 7; i < argc; ++i) {
+      if (!strcmp(argv[i], "--validate")) { validate = true; continue; }
+      if (i + 1 >= argc) break;
       if (!strcmp(argv[i], "--s-file")) s_file = argv[i + 1];
       else if (!strcmp(argv[i], "--s-seed")) s_seed = strtoull(argv[i + 1], nullptr, 0);
+      ++i;
     }
-    try { return complete_proof(curve, argv[3], argv[4], argv[5], argv[6], s_file, s_seed); }
+    try {
+      if (validate) { if (int rc = validate_completion(curve, argv[3], argv[4], argv[5])) return rc; }
+      return complete_proof(curve, argv[3], argv[4], argv[5], argv[6], s_file, s_seed);
+    }
     catch (const std::exception& e) { fprintf(stderr, "main_hip: %s\n", e.what()); return 1; }
   }
   if (argc >= 3 && !strcmp(argv[2], "self-test")) {
@@ -326,6 +439,31 @@ int main(int argc, char** argv) {
     printf("self-test: all known answers of the reference agree (level 2)\n");
     return 0;
   }
+  if (argc >= 3 && (!strcmp(argv[2], "check") || !strcmp(argv[2], "check-r1cs"))) {
+    const bool with_r1cs = !strcmp(argv[2], "check-r1cs");
+    std::vector<const char*> pos;
+    for (int i = 3; i < argc; ++i) {
+      if (!strcmp(argv[i], "--gpus") && i + 1 < argc) { g_gpus = atoi(argv[++i]); continue; }
+      if (argv[i][0] == '-') { fprintf(stderr, "main_hip: unknown option %s\n", argv[i]); return 2; }
+      pos.push_back(argv[i]);
+    }
+    if (with_r1cs ? pos.size() != 3 : (pos.empty() || pos.size() > 2)) {
+      fprintf(stderr, "usage: %s MNT4753|MNT6753 check <params> [<input>] [--gpus N]\n       %s MNT4753|MNT6753 check-r1cs <params> <r1cs> <witness> [--gpus N]\n", argv[0], argv[0]);
+      return 2;
+    }
+    const char* input = with_r1cs ? pos[2] : (pos.size() > 1 ? pos[1] : nullptr);
+    const char* r1cs = with_r1cs ? pos[1] : nullptr;
+    try {
+      if (!strcmp(argv[1], "MNT4753")) return run_check<mnt4753_hip>(pos[0], input, r1cs);
+      if (!strcmp(argv[1], "MNT6753")) return run_check<mnt6753_hip>(pos[0], input, r1cs);
+      fprintf(stderr, "unknown curve %s\n", argv[1]);
+      return 2;
+    } catch (const std::exception& e) {
+      fprintf(stderr, "main_hip: %s\n", e.what());
+      return 1;
+    }
+  }
+  if (const char* e = getenv("MNT753_VALIDATE")) g_validate = atoi(e) != 0;
   if (argc < 6) {
     fprintf(stderr, "usage: %s MNT4753|MNT6753 compute <params> <input> <output> [<input2> <output2> ...] [--repeat N] [--serve] [--gpus N] [--tables | --one-shot] [--unfused-h] [--unfused-c] [--ref-order] [--fold rccl|host] [--quiet]\n"
                     "  further (input, output) pairs and --repeat prove against the parameters that are already resident on the GPU\n", argv[0]);
@@ -357,6 +495,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--peer-bench")) g_peer_bench = true;
     else if (!strcmp(argv[i], "--tables")) g_one_shot = 0;      // build the window tables even for a single proof
     else if (!strcmp(argv[i], "--one-shot")) g_one_shot = 1;    // no window tables, no warm-up MSM, whatever the job list
+    else if (!strcmp(argv[i], "--validate")) g_validate = true;
     else {
       // an option this prover does not have (or one that lost its argument), or an input without its output: refuse, do not guess
       fprintf(stderr, argv[i][0] == '-' ? "main_hip: unknown option %s\n" : "main_hip: input %s without an output path\n", argv[i]);
@@ -368,9 +507,9 @@ int main(int argc, char** argv) {
     if (mode != "compute" && mode != "compute-r1cs") { fprintf(stderr, "unknown mode %s\n", argv[2]); return 2; }
     if (repeat > 1) { const auto one = jobs; for (int k = 1; k < repeat; ++k) jobs.insert(jobs.end(), one.begin(), one.end()); }
     const char* r1cs_path = with_r1cs ? argv[4] : nullptr;
-    if (curve == "MNT4753") run_prover<mnt4753_hip>(argv[3], jobs, r1cs_path);
-    else if (curve == "MNT6753") run_prover<mnt6753_hip>(argv[3], jobs, r1cs_path);
-    else { fprintf(stderr, "unknown curve %s\n", argv[1]); return 2; }
+    if (curve == "MNT4753") return run_prover<mnt4753_hip>(argv[3], jobs, r1cs_path);
+    if (curve == "MNT6753") return run_prover<mnt6753_hip>(argv[3], jobs, r1cs_path);
+    fprintf(stderr, "unknown curve %s\n", argv[1]); return 2;
   } catch (const std::exception& e) {
     fprintf(stderr, "main_hip: %s\n", e.what());
     return 1;

@@ -1240,5 +1240,140 @@ template <int CURVE> double HIP_B::input_load_seconds(groth16_input* in) {
 template <int CURVE> const uint64_t* HIP_B::G1_words(const G1* a) { resolve<CURVE>(const_cast<G1*>(a)); return a->data; }
 template <int CURVE> const uint64_t* HIP_B::G2_words(const G2* a) { resolve<CURVE>(const_cast<G2*>(a)); return a->data; }
 
+// ---- input validation (include/prover_hip_functions.hpp) -----------------------------------------------------------------------------
+template <int CURVE> const char* HIP_B::check_reason_text(int reason) {
+  switch (reason) {
+    case MNT753_BAD_NONE: return "ok";
+    case MNT753_BAD_NONCANONICAL: return "not canonical";
+    case MNT753_BAD_OFF_CURVE: return "off curve";
+    case MNT753_BAD_UNSATISFIED: return "not satisfied";
+    default: return "unknown reason";
+  }
+}
+namespace {
+// a block of device memory for the length of one check (not parked in the buffer cache: nothing of this size comes again)
+struct CheckBlock {
+  void* ptr = nullptr;
+  explicit CheckBlock(size_t bytes) { check(mnt753_dev_alloc(&ptr, bytes ? bytes : 16), "mnt753_dev_alloc"); }
+  ~CheckBlock() { if (ptr) mnt753_dev_free(ptr); }
+  CheckBlock(const CheckBlock&) = delete;
+  CheckBlock& operator=(const CheckBlock&) = delete;
+};
+// d, m of a parameter file, checked against its size like the loader does
+void params_header(const char* path, int curve, size_t* d, size_t* m) {
+  FILE* f = fopen(path, "rb");
+  if (!f) throw std::runtime_error(std::string("cannot open params file ") + path);
+  uint64_t dm[2];
+  read_exact(f, dm, 16, path);
+  fclose(f);
+  const size_t g1w = mnt753_affine_words(curve, MNT753_G1), g2w = mnt753_affine_words(curve, MNT753_G2);
+  struct stat st;
+  if (dm[1] < 2 || dm[0] < 1 || dm[1] > ((uint64_t)1 << 31) || dm[0] > ((uint64_t)1 << 31) || stat(path, &st) != 0)
+    throw std::runtime_error(std::string("bad params header (d, m) in ") + path);
+  const unsigned long long expect = 16ull + 8ull * ((unsigned long long)g1w * (3ull * dm[1] + dm[0] + 1ull) + (unsigned long long)g2w * (dm[1] + 1ull));
+  if ((unsigned long long)st.st_size != expect)
+    throw std::runtime_error(std::string("params file size does not match its header (d=") + std::to_string(dm[0]) + ", m=" + std::to_string(dm[1]) + "): " + path);
+  *d = (size_t)dm[0]; *m = (size_t)dm[1];
+}
+template <class Report> void add_entry(Report& rep, const char* set, size_t size, const mnt753_check_report& r) {
+  rep.sets[rep.n_sets++] = {set, size, r.n_bad, r.first_bad, (int)r.first_reason};
+}
+}  // namespace
+template <int CURVE> typename HIP_B::check_report HIP_B::check_params_file(const char* path) {
+  size_t d = 0, m = 0;
+  params_header(path, CURVE, &d, &m);
+  const size_t g1w = mnt753_affine_words(CURVE, MNT753_G1), g2w = mnt753_affine_words(CURVE, MNT753_G2);
+  const int n_dev = std::max(1, mnt753_device_count());
+  struct Set { const char* name; int group; size_t words, n, off; };
+  const size_t off_B1 = 16 + 8 * g1w * (m + 1), off_B2 = off_B1 + 8 * g1w * (m + 1), off_L = off_B2 + 8 * g2w * (m + 1), off_H = off_L + 8 * g1w * (m - 1);
+  const Set sets[5] = {{"A", MNT753_G1, g1w, m + 1, 16}, {"B1", MNT753_G1, g1w, m + 1, off_B1}, {"B2", MNT753_G2, g2w, m + 1, off_B2},
+                       {"L", MNT753_G1, g1w, m - 1, off_L}, {"H", MNT753_G1, g1w, d, off_H}};
+  check_report rep;
+  for (const Set& s : sets) {
+    mnt753_check_report total{0, 0, MNT753_BAD_NONE, 0};
+    // slice g on device g, as the base sets are cut (slice_bounds); indices are reported in file order
+    for (int g = 0; g < n_dev; ++g) {
+      size_t lo, hi;
+      slice_bounds(s.n, n_dev, g, &lo, &hi);
+      if (hi == lo) continue;
+      DeviceScope on(g);
+      CheckBlock blk(8 * s.words * (hi - lo));
+      check(mnt753_load_file_to_device(path, s.off + 8 * s.words * lo, 8 * s.words * (hi - lo), blk.ptr), "mnt753_load_file_to_device");
+      mnt753_check_report r;
+      check(mnt753_check_points(CURVE, s.group, reinterpret_cast<const uint64_t*>(blk.ptr), 1, hi - lo, &r, nullptr), "mnt753_check_points");
+      if (r.n_bad && !total.n_bad) { total.first_bad = lo + r.first_bad; total.first_reason = r.first_reason; }
+      total.n_bad += r.n_bad;
+    }
+    add_entry(rep, s.name, s.n, total);
+  }
+  return rep;
+}
+template <int CURVE> typename HIP_B::check_report HIP_B::check_params(groth16_params* p) { return check_params_file(p->path.c_str()); }
+
+// w, ca, cb, cc, r canonical; then the rows: ca[i] cb[i] = cc[i] on the vectors as they lie on the device, or -- cs given -- the
+// system evaluated on w once more (mnt753_r1cs_check)
+template <int CURVE> static typename HIP_B::check_report check_input_impl(typename HIP_B::groth16_input* in, R1csHolder* cs) {
+  typename HIP_B::check_report rep;
+  in->w_ready->wait(); in->ca_ready->wait(); in->cb_ready->wait(); in->cc_ready->wait();
+  auto scalars = [&](const char* name, const std::shared_ptr<DeviceBuffer>& buf, size_t n) {
+    DeviceScope on(buf->device);
+    mnt753_check_report r;
+    check(mnt753_check_scalars(CURVE, reinterpret_cast<const uint64_t*>(buf->ptr), 1, n, &r, nullptr), "mnt753_check_scalars");
+    add_entry(rep, name, n, r);
+  };
+  scalars("w", in->w, in->n_w);
+  if (!cs) { scalars("ca", in->ca, in->n_c); scalars("cb", in->cb, in->n_c); scalars("cc", in->cc, in->n_c); }
+  mnt753_check_report r;
+  check(mnt753_check_scalars(CURVE, in->r, 0, 1, &r, nullptr), "mnt753_check_scalars");
+  add_entry(rep, "r", 1, r);
+  if (cs) {
+    DeviceScope on(in->w->device);
+    check(mnt753_r1cs_check(cs->h, reinterpret_cast<const uint64_t*>(in->w->ptr), &r, nullptr), "mnt753_r1cs_check");
+    add_entry(rep, "constraints", mnt753_r1cs_domain_size(cs->h) - mnt753_r1cs_num_inputs(cs->h) - 1, r);
+    return rep;
+  }
+  // cb / cc of a sharded prover live on devices 1 / 2: the rows are checked where ca lives
+  const int home = in->ca->device;
+  DeviceScope on(home);
+  std::unique_ptr<CheckBlock> tb, tc;
+  const uint64_t *pb = reinterpret_cast<const uint64_t*>(in->cb->ptr), *pc = reinterpret_cast<const uint64_t*>(in->cc->ptr);
+  if (in->cb->device != home) {
+    tb.reset(new CheckBlock(96 * in->n_c));
+    check(mnt753_copy_peer(home, tb->ptr, in->cb->device, in->cb->ptr, 96 * in->n_c), "mnt753_copy_peer");
+    pb = reinterpret_cast<const uint64_t*>(tb->ptr);
+  }
+  if (in->cc->device != home) {
+    tc.reset(new CheckBlock(96 * in->n_c));
+    check(mnt753_copy_peer(home, tc->ptr, in->cc->device, in->cc->ptr, 96 * in->n_c), "mnt753_copy_peer");
+    pc = reinterpret_cast<const uint64_t*>(tc->ptr);
+  }
+  check(mnt753_check_products(CURVE, reinterpret_cast<const uint64_t*>(in->ca->ptr), pb, pc, in->n_c, &r, nullptr), "mnt753_check_products");
+  add_entry(rep, "constraints", in->n_c, r);
+  return rep;
+}
+template <int CURVE> typename HIP_B::check_report HIP_B::check_input(groth16_input* in, groth16_params*) { return check_input_impl<CURVE>(in, nullptr); }
+template <int CURVE> typename HIP_B::check_report HIP_B::check_input_file(const char* params_path, const char* input_path) {
+  size_t d = 0, m = 0;
+  params_header(params_path, CURVE, &d, &m);
+  check_report rep;
+  {
+    groth16_input in(input_path, d, m);
+    rep = check_input_impl<CURVE>(&in, nullptr);
+  }
+  g_buffers.release_all();
+  return rep;
+}
+template <int CURVE> typename HIP_B::check_report HIP_B::check_witness_file(const char* params_path, r1cs* cs, const char* witness_path) {
+  size_t d = 0, m = 0;
+  params_header(params_path, CURVE, &d, &m);
+  check_report rep;
+  {
+    groth16_input in(witness_path, d, m, cs->data);
+    rep = check_input_impl<CURVE>(&in, cs->data.get());
+  }
+  g_buffers.release_all();
+  return rep;
+}
+
 template class mnt753_hip_impl<0>;
 template class mnt753_hip_impl<1>;

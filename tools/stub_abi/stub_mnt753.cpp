@@ -180,5 +180,41 @@ int mnt753_r1cs_evaluate(mnt753_r1cs* r, const uint64_t* w, uint64_t* a, uint64_
   if (!r || !w || !a || !b || !c) return fail(MNT753_EINVAL, "r1cs_evaluate: null");
   touch(const_cast<uint64_t*>(w), r->m + 1); memset(a, 0, 96 * n); memset(b, 0, 96 * n); memset(c, 0, 96 * n); return 0;
 }
+// input validation: no arithmetic here either, so every input is "good" -- unless MNT753_STUB_BAD_POINT=<index> asks for one bad
+// point (off curve) at that index of every point set long enough to have it, MNT753_STUB_BAD_ROW=<row> for one unsatisfied row.
+// The ranges are touched like everywhere else: ASan / TSan see the reads the kernels would make.
+static void touch_ro(const uint64_t* v, size_t words) { volatile uint64_t s = 0; for (size_t i = 0; i < words; i += 12) s += v[i]; (void)s; }
+static void stub_report(mnt753_check_report* out, const char* env, size_t n, uint32_t reason) {
+  *out = mnt753_check_report{0, 0, MNT753_BAD_NONE, 0};
+  const char* e = getenv(env);
+  if (e && *e && strtoull(e, nullptr, 0) < n) *out = mnt753_check_report{1, strtoull(e, nullptr, 0), reason, 0};
+}
+int mnt753_check_points(int curve, int group, const uint64_t* aff, int, size_t n, mnt753_check_report* out, void*) {
+  if (bad_cg(curve, group) || !out || (n && !aff)) return fail(MNT753_EINVAL, "check_points: bad argument");
+  if (!g_ndev) return fail(MNT753_ENODEV, "no device");
+  touch_ro(aff, n * mnt753_affine_words(curve, group));
+  stub_report(out, "MNT753_STUB_BAD_POINT", n, MNT753_BAD_OFF_CURVE);
+  return 0;
+}
+int mnt753_check_scalars(int curve, const uint64_t* fr, int, size_t n, mnt753_check_report* out, void*) {
+  if (curve < 0 || curve > 1 || !out || (n && !fr)) return fail(MNT753_EINVAL, "check_scalars: bad argument");
+  if (!g_ndev) return fail(MNT753_ENODEV, "no device");
+  touch_ro(fr, 12 * n);
+  *out = mnt753_check_report{0, 0, MNT753_BAD_NONE, 0};
+  return 0;
+}
+int mnt753_check_products(int curve, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t n, mnt753_check_report* out, void*) {
+  if (curve < 0 || curve > 1 || !out || (n && (!a || !b || !c))) return fail(MNT753_EINVAL, "check_products: bad argument");
+  if (!g_ndev) return fail(MNT753_ENODEV, "no device");
+  touch_ro(a, 12 * n); touch_ro(b, 12 * n); touch_ro(c, 12 * n);
+  stub_report(out, "MNT753_STUB_BAD_ROW", n, MNT753_BAD_UNSATISFIED);
+  return 0;
+}
+int mnt753_r1cs_check(mnt753_r1cs* r, const uint64_t* w, mnt753_check_report* out, void*) {
+  if (!r || !w || !out) return fail(MNT753_EINVAL, "r1cs_check: null argument");
+  touch_ro(w, 12 * (r->m + 1));
+  stub_report(out, "MNT753_STUB_BAD_ROW", r->nc, MNT753_BAD_UNSATISFIED);
+  return 0;
+}
 int mnt753_synth_scalars(int, uint64_t seed, size_t n, uint64_t* out) { for (size_t i = 0; i < 12 * n; ++i) out[i] = seed + i; return 0; }
 }

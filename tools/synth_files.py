@@ -1,7 +1,10 @@
 """Write a synthetic parameter file + input file in the reference's exact layout
 (libsnark/generate_parameters.cpp:60-108) from the library's deterministic generators.  The reference prover
 never validates its inputs, so it (and the oracle) accept these files; they stand in for generate_parameters
-output on machines that have neither the reference nor its 1.2 GB parameter files."""
+output on machines that have neither the reference nor its 1.2 GB parameter files.
+`main_hip --validate` / `main_hip <curve> check <params> <input>` do NOT accept the input file: its points and scalars are well
+formed (multiples of the generator, uniform elements below r), but ca, cb, cc are three independent random vectors, so no row
+satisfies ca[i] cb[i] = cc[i] -- `constraint 0 of d + 1 is not satisfied`, which is the right verdict on these files."""
 import os
 import sys
 
