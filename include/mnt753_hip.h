@@ -196,8 +196,12 @@ int mnt753_point_from_affine(int curve, int group, const uint64_t* affine, uint6
 
 /* ---- FFT over Fr ---------------------------------------------------------------------------------- */
 typedef struct mnt753_domain mnt753_domain;
-/* libfqfft's basic_radix2_domain of exactly m elements: m must be a power of two <= 2^s (s = 30 MNT4753, 15 MNT6753),
- * MNT753_EDOMAIN otherwise.  (B::get_evaluation_domain goes through mnt753_domain_create_for.) */
+/* libfqfft's basic_radix2_domain of exactly m elements: the constructor accepts every power of two m <= 2^s (s = 30 MNT4753,
+ * 15 MNT6753), MNT753_EDOMAIN otherwise.  2^25 (MNT4753) is the largest size compared with the reference -- every schedule of
+ * the transform kernel up to its first four-launch one, tests/test_fft_schedules_gpu.py; nothing above it has been run.  A domain
+ * holds 544 bytes of device memory per element (two twiddle tables of m / 2 and three coset tables of m entries of 112 bytes, a
+ * work vector of m elements of 96): 18.3 GB at 2^25, beside the caller's vectors of 96 bytes per element.
+ * (B::get_evaluation_domain goes through mnt753_domain_create_for.) */
 int mnt753_domain_create(int curve, size_t m, mnt753_domain** out);
 /* replaces B::get_evaluation_domain (hpp:30) = libfqfft get_evaluation_domain(min_size): the first of basic_radix2_domain,
  * extended_radix2_domain (2^(s+1): two size-2^s transforms, the second on the coset shift * <omega>) and step_radix2_domain
@@ -220,7 +224,8 @@ size_t mnt753_domain_size(const mnt753_domain* d);   /* B::domain_get_m (hpp:47)
 int mnt753_fft(mnt753_domain* d, int kind, uint64_t* dev_vec, void* stream);
 /* replaces B::domain_divide_by_Z_on_coset (hpp:46) */
 int mnt753_divide_by_z_on_coset(mnt753_domain* d, uint64_t* dev_vec, void* stream);
-/* replaces B::vector_Fr_muleq / vector_Fr_subeq (hpp:35-36): a[i] = a[i] (*|-) b[i], i < n */
+/* replaces B::vector_Fr_muleq / vector_Fr_subeq (hpp:35-36): a[i] = a[i] (*|-) b[i], i < n.  dev_b may be dev_a itself, as in
+ * the reference's loops (the squares in place / all zeros); otherwise the two vectors must not overlap. */
 int mnt753_vec_muleq(int curve, uint64_t* dev_a, const uint64_t* dev_b, size_t n, void* stream);
 int mnt753_vec_subeq(int curve, uint64_t* dev_a, const uint64_t* dev_b, size_t n, void* stream);
 /* dst[i] = src[i] * k, i < n, k one Fr element in HOST memory (wire format); dst may be src.  Used to fold the factor r of
