@@ -206,14 +206,33 @@ int mnt753_domain_create(int curve, size_t m, mnt753_domain** out);
 /* replaces B::get_evaluation_domain (hpp:30) = libfqfft get_evaluation_domain(min_size): the first of basic_radix2_domain,
  * extended_radix2_domain (2^(s+1): two size-2^s transforms, the second on the coset shift * <omega>) and step_radix2_domain
  * (2^k + 2^r) that accepts min_size, then the same three at big + rounded_small, which may be larger than min_size
- * (mnt753_domain_size says).  Every call that takes a domain works on all three kinds.  MNT753_EDOMAIN, with a message naming
+ * (mnt753_domain_size says).  Every call that takes a domain works on all kinds.  MNT753_EDOMAIN, with a message naming
  * the size and the reference's domain, wherever the reference's walk stops at a domain this library does not build: a
  * mixed-radix basic domain (MNT6753 only: its Fr accepts 2^a 5^b, a <= 15, b <= 2, so 5, 10, 25, 40, 5 * 2^15 are refused,
  * not stepped) or the candidates behind the first six (mixed-radix best fit, geometric and arithmetic sequence domains). */
 #define MNT753_DOMAIN_BASIC 0
 #define MNT753_DOMAIN_EXTENDED 1
 #define MNT753_DOMAIN_STEP 2
-int mnt753_domain_create_for(int curve, size_t min_size, mnt753_domain** out);
+#define MNT753_DOMAIN_MIXED 3
+int mnt753_domain_create_for(int curve, size_t min_size, mnt753_domain** out);   /* == mnt753_domain_create_for_ex(curve, min_size, 0, out) */
+/* The same walk with the mixed-radix basic domains of MNT6753 built instead of refused (flags = MNT753_DOMAIN_ALLOW_MIXED): wherever
+ * the walk above stops at "a mixed-radix basic_radix2_domain" -- candidates 1 and 4 (the basic domain at min_size or at big +
+ * rounded_small) and candidate 7 (best_mixed_domain_size, get_evaluation_domain.tcc:35-56, 110-118: the smallest 2^a 5^b >= min_size,
+ * which may be larger than min_size) -- it returns a domain of kind MNT753_DOMAIN_MIXED.  That reaches 25 * 2^15 = 819200 on MNT6753,
+ * where the radix-2 kinds end at 2^16.  Still refused, with the same messages: an extended domain over a mixed-radix half, the
+ * sequence domains, sizes 0 and 1.  The flag is an argument of the call, there is no process-wide switch; it changes nothing on
+ * MNT4753, whose Fr has no small subgroup.  Unknown flag bits: MNT753_EINVAL. */
+#define MNT753_DOMAIN_ALLOW_MIXED 1u
+int mnt753_domain_create_for_ex(int curve, size_t min_size, unsigned flags, mnt753_domain** out);
+/* libfqfft's basic_radix2_domain of exactly m = 2^a 5^b elements, 0 <= a <= 15, 1 <= b <= 2, on MNT6753 (mnt6753_init.cpp:73-76
+ * declares the small subgroup of order 5^2; basic_radix2_domain.tcc:26-60 accepts, basic_radix2_domain_aux.tcc:46-165 transforms):
+ * the exact-size sibling of mnt753_domain_create, which keeps the powers of two.  MNT753_EDOMAIN for any other size and for every
+ * size on MNT4753.  omega = get_root_of_unity(m) (field_utils.tcc:59-70), the coset shift g = 17 as in the other kinds.  The
+ * transform is the m / 5^b-point radix-2 transform of a basic domain, 5^b times, and b radix-5 passes (csrc/ntt_kernels.hip.h,
+ * DESIGN.md section 4.5).  Device memory: 544 bytes per element (the powers of omega, omega^-1, g and g^-1, m entries of 112
+ * bytes each, and a work vector of m elements of 96) plus the inner radix-2 domain of m / 5^b elements at 208 bytes each: 586 bytes
+ * per element for b = 1, 552 for b = 2 -- 480 MB at 819200. */
+int mnt753_domain_create_mixed(int curve, size_t m, mnt753_domain** out);
 int mnt753_domain_kind(const mnt753_domain* d);      /* MNT753_DOMAIN_*; -1 for a null domain */
 int mnt753_domain_free(mnt753_domain* d);
 size_t mnt753_domain_size(const mnt753_domain* d);   /* B::domain_get_m (hpp:47) */

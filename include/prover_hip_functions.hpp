@@ -120,6 +120,11 @@ public:
   // resident prover (--repeat / --serve / several jobs), never in one.  Same proof bytes.  main_hip sets it for a single job on one
   // device; MNT753_ONE_SHOT=0 / 1 and MNT753_MSM_PRECOMP=0 / 1 override.  Call before read_params.
   static void one_shot(bool on);
+  // true: get_evaluation_domain also builds the mixed-radix basic domains of MNT6753 (2^a 5^b, up to 819200 elements: libfqfft's
+  // basic_radix2_domain over the small subgroup of Fr, candidates 1, 4 and 7 of get_evaluation_domain) where it otherwise throws
+  // with the library's message -- mnt753_domain_create_for_ex with MNT753_DOMAIN_ALLOW_MIXED.  Off by default; nothing changes on
+  // MNT4753.  main_hip --mixed-radix / MNT753_MIXED_RADIX=1.  Call before read_params and get_evaluation_domain.
+  static void allow_mixed_radix(bool on);
   // The step before the hot path: instead of reading ca / cb / cc from the input file (where the
   // reference's generator put them, generate_parameters.cpp:44-57), evaluate the constraint system on the assignment on the
   // device -- the first loop of r1cs_to_qap_witness_map (reductions/r1cs_to_qap/r1cs_to_qap.tcc:223-237).

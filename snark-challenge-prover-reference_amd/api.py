@@ -87,6 +87,8 @@ def lib():
         "mnt753_point_from_affine": (i, [i, i, u64p, u64p]),
         "mnt753_domain_create": (i, [i, sz, C.POINTER(vp)]),
         "mnt753_domain_create_for": (i, [i, sz, C.POINTER(vp)]),
+        "mnt753_domain_create_for_ex": (i, [i, sz, C.c_uint, C.POINTER(vp)]),
+        "mnt753_domain_create_mixed": (i, [i, sz, C.POINTER(vp)]),
         "mnt753_domain_kind": (i, [vp]),
         "mnt753_domain_free": (i, [vp]),
         "mnt753_domain_size": (sz, [vp]),
@@ -332,9 +334,12 @@ class DeviceBuffer:
 class Domain:
     """An evaluation domain over Fr of the curve.  Domain(curve, m): libfqfft's basic_radix2_domain of exactly m elements (a power of
     two).  Domain.for_size(curve, min_size): the domain libfqfft's get_evaluation_domain(min_size) builds (B::get_evaluation_domain) --
-    basic, extended (2^(s+1)) or step (2^k + 2^r) radix-2; its size `m` may be larger than min_size."""
+    basic, extended (2^(s+1)) or step (2^k + 2^r) radix-2; its size `m` may be larger than min_size.  With mixed=True the walk also
+    builds the mixed-radix basic domains of MNT6753 (2^a 5^b, a <= 15, b <= 2: up to 819200 elements) where it otherwise stops with
+    an error.  Domain.mixed(curve, m): that domain at exactly m elements."""
 
-    BASIC, EXTENDED, STEP = 0, 1, 2
+    BASIC, EXTENDED, STEP, MIXED = 0, 1, 2, 3
+    ALLOW_MIXED = 1
 
     def __init__(self, curve, m):
         self.curve, self.m = curve, int(m)
@@ -342,17 +347,28 @@ class Domain:
         _check(lib().mnt753_domain_create(curve, self.m, C.byref(self._h)), "mnt753_domain_create")
 
     @classmethod
-    def for_size(cls, curve, min_size):
+    def for_size(cls, curve, min_size, mixed=False):
         self = cls.__new__(cls)
         self.curve = curve
         self._h = C.c_void_p()
-        _check(lib().mnt753_domain_create_for(curve, int(min_size), C.byref(self._h)), "mnt753_domain_create_for")
+        if mixed:
+            _check(lib().mnt753_domain_create_for_ex(curve, int(min_size), cls.ALLOW_MIXED, C.byref(self._h)), "mnt753_domain_create_for_ex")
+        else:
+            _check(lib().mnt753_domain_create_for(curve, int(min_size), C.byref(self._h)), "mnt753_domain_create_for")
         self.m = int(lib().mnt753_domain_size(self._h))
+        return self
+
+    @classmethod
+    def mixed(cls, curve, m):
+        self = cls.__new__(cls)
+        self.curve, self.m = curve, int(m)
+        self._h = C.c_void_p()
+        _check(lib().mnt753_domain_create_mixed(curve, self.m, C.byref(self._h)), "mnt753_domain_create_mixed")
         return self
 
     @property
     def kind(self):
-        """Domain.BASIC, Domain.EXTENDED or Domain.STEP."""
+        """Domain.BASIC, Domain.EXTENDED, Domain.STEP or Domain.MIXED."""
         return int(lib().mnt753_domain_kind(self._h))
 
     def fft(self, kind, dev_ptr, stream=None):

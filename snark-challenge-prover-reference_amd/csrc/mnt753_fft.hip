@@ -40,6 +40,11 @@ struct mnt753_domain {
   uint32_t *xconsts = nullptr;                         // step: 1/(2 big_m), 1/(2 small_m), 1/big_m, 2^12    extended: shift^s, sconst, -, 2^12
   uint32_t *zt = nullptr, *zt12 = nullptr;             // 1/Z on the coset and 2^-12 times it: z_mask + 2 entries each (z_index)
   size_t z_split = 0, z_mask = 0;
+  // mixed-radix domain (m = q_n t_n, q_n = 5^q_pow, t_n a power of two): sub_big is the inner basic domain of size t_n (null where
+  // t_n is 1).  x_fwd / x_inv: omega^k / omega^-k (m each), xcos_fwd / xcos_inv as above, xconsts: zeta^e, zeta^-e, zeta^-e / m
+  // (e < 5 each), consts as in a basic domain (Z is one constant).  The step / extended fields above stay unused.
+  unsigned q_n = 0, q_pow = 0;
+  size_t t_n = 0;
 };
 
 namespace {
@@ -150,9 +155,46 @@ int x_inner(mnt753_domain* d, const uint32_t* from, uint32_t* to, bool inverse, 
   HIP_TRY(hipMemcpyAsync(to + d->big_m * 24, from + d->big_m * 24, 96, hipMemcpyDeviceToDevice, st));
   return 0;
 }
+// mixed-radix domain, all four kinds: digit split (out of place, vec -> work), q_n inner radix-2 transforms (work -> vec), q_pow
+// radix-5 levels in place on vec (ntt_kernels.hip.h).  The inverse is the same schedule over omega^-1; its 1 / m rides on the last
+// level's constants and icosetFFT's g^-k on that level's stores.
+template <int M>
+int mixed_transform(mnt753_domain* d, uint32_t* vec, bool inverse, bool coset, hipStream_t st) {
+  const size_t m = d->m, t_n = d->t_n;
+  const unsigned gb = (unsigned)((m + 255) / 256);
+  if (coset && !inverse) hipLaunchKernelGGL((k_mixed_pre<M, true>), dim3(gb), dim3(256), 0, st, vec, d->work, d->xcos_fwd, m, d->q_n, t_n);
+  else hipLaunchKernelGGL((k_mixed_pre<M, false>), dim3(gb), dim3(256), 0, st, vec, d->work, d->xcos_fwd, m, d->q_n, t_n);
+  HIP_TRY(hipGetLastError());
+  if (mnt753_domain* in = d->sub_big) {
+    for (unsigned s = 0; s < d->q_n; ++s)
+      if (int rc = run_stages<M>(in, d->work + s * t_n * 24, vec + s * t_n * 24, inverse ? in->tw_inv : in->tw_fwd, st)) return rc;
+  } else {
+    HIP_TRY(hipMemcpyAsync(vec, d->work, m * 96, hipMemcpyDeviceToDevice, st));      // t_n == 1: the inner transforms are the identity
+  }
+  const size_t n_cols = m / 5;
+  const unsigned blocks = (unsigned)((n_cols + R5_COLS - 1) / R5_COLS);
+  const uint32_t* tw = inverse ? d->x_inv : d->x_fwd;
+  size_t width = t_n;
+  for (unsigned lvl = 0; lvl < d->q_pow; ++lvl, width *= 5) {
+    const bool last = lvl + 1 == d->q_pow;
+    const size_t tw_stride = m / (5 * width);
+    if (inverse && last) {
+      const uint32_t* zc = d->xconsts + 10 * FPS_WORDS;
+      if (coset) hipLaunchKernelGGL((k_radix5_merge<M, true, true>), dim3(blocks), dim3(R5_BLOCK), 0, st, vec, tw, zc, d->xcos_inv, n_cols, width, tw_stride);
+      else hipLaunchKernelGGL((k_radix5_merge<M, true, false>), dim3(blocks), dim3(R5_BLOCK), 0, st, vec, tw, zc, d->xcos_inv, n_cols, width, tw_stride);
+    } else {
+      const uint32_t* zc = d->xconsts + (inverse ? 5 : 0) * FPS_WORDS;
+      hipLaunchKernelGGL((k_radix5_merge<M, false, false>), dim3(blocks), dim3(R5_BLOCK), 0, st, vec, tw, zc, d->xcos_inv, n_cols, width, tw_stride);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // FFT (coset: cosetFFT), in place on vec through the domain's work buffer
 template <int M>
 int x_forward(mnt753_domain* d, uint32_t* vec, bool coset, hipStream_t st) {
+  if (d->kind == MNT753_DOMAIN_MIXED) return mixed_transform<M>(d, vec, false, coset, st);
   if (d->kind == MNT753_DOMAIN_STEP) {
     const StepGrid g = step_grid(d);
     if (coset) hipLaunchKernelGGL((k_step_pre<M, true>), dim3(g.blocks), dim3(g.threads), 0, st, vec, d->work, d->x_fwd, d->xcos_fwd, d->big_m, d->small_m, g.ti_n, g.tj_n);
@@ -168,6 +210,7 @@ int x_forward(mnt753_domain* d, uint32_t* vec, bool coset, hipStream_t st) {
 // iFFT (coset: icosetFFT)
 template <int M>
 int x_inverse(mnt753_domain* d, uint32_t* vec, bool coset, hipStream_t st) {
+  if (d->kind == MNT753_DOMAIN_MIXED) return mixed_transform<M>(d, vec, true, coset, st);
   if (int rc = x_inner<M>(d, vec, d->work, true, st)) return rc;
   if (d->kind == MNT753_DOMAIN_STEP) {
     const StepGrid g = step_grid(d);
@@ -231,7 +274,10 @@ template <int M>
 int h_finish_t(mnt753_domain* d, uint32_t* ca, const uint32_t* cb, const uint32_t* cc, uint32_t* h, hipStream_t st) {
   const size_t m = d->m;
   const unsigned gb = (unsigned)((m + 255) / 256);
-  if (d->kind != MNT753_DOMAIN_BASIC) {
+  if (d->kind == MNT753_DOMAIN_MIXED) {       // Z on the coset is the one constant g^m - 1, as in the basic domain
+    hipLaunchKernelGGL((k_h_pointwise<M>), dim3(gb), dim3(256), 0, st, ca, cb, cc, d->consts + 1 * FPS_WORDS, d->consts + 2 * FPS_WORDS, m);
+    if (int rc = x_inverse<M>(d, ca, true, st)) return rc;
+  } else if (d->kind != MNT753_DOMAIN_BASIC) {
     hipLaunchKernelGGL((k_h_pointwise_ztab<M>), dim3(gb), dim3(256), 0, st, ca, cb, cc, d->xconsts + 3 * FPS_WORDS, d->zt12, d->z_split, d->z_mask, m);
     if (int rc = x_inverse<M>(d, ca, true, st)) return rc;
   } else {
@@ -384,10 +430,75 @@ int create_outer(int curve, int frm, int kind, size_t m, mnt753_domain** out) {
   return 0;
 }
 
+// tables of a mixed-radix domain (q_n, q_pow, t_n set; the inner domain exists where t_n > 1)
+template <int M>
+int build_mixed(mnt753_domain* d) {
+  typedef HFp<M> Fr;
+  const size_t m = d->m;
+  const Fr one = Fr::one();
+  // omega = get_root_of_unity(m): full_root_of_unity to the 5th power (2 - b) times, then squared (s - a) times (field_utils.tcc:59-70)
+  Fr omega = Fr::from_words(FR_FULL_ROOT_B);
+  for (unsigned i = d->q_pow; i < (unsigned)FR_SMALL_SUBGROUP_POWER_B; ++i) omega = omega.pow_u64(FR_SMALL_SUBGROUP_BASE_B);
+  for (int i = FRD[M].two_adicity; i > ceil_log2(d->t_n); --i) omega = omega.squared();
+  const Fr omega_inv = omega.inverse();
+  const Fr g = Fr::from_words(FRD[M].mult_gen), g_inv = g.inverse();
+  const Fr minv = Fr::from_uint((uint64_t)m).inverse();
+  const Fr zinv = (g.pow_u64((uint64_t)m) - one).inverse();      // basic_radix2_domain.tcc:113-116
+  const Fr two12 = Fr::from_uint(4096), two12_inv = two12.inverse();
+  const Fr zeta = omega.pow_u64((uint64_t)(m / 5)), zeta_inv = zeta.inverse();
+  // staging (host, wire form): 4 power tables of 32 entries, the scale 1, 15 radix-5 constants, the 4 constants of a basic domain
+  std::vector<uint64_t> stage((4 * 32 + 1 + 15 + 4) * 12);
+  auto put = [&](size_t slot, const Fr& v) { memcpy(&stage[slot * 12], v.l, 96); };
+  const Fr bases[4] = {omega, omega_inv, g, g_inv};
+  for (int t = 0; t < 4; ++t) {
+    Fr p = bases[t];
+    for (int b = 0; b < 32; ++b) { put(t * 32 + b, p); p = p.squared(); }
+  }
+  put(128, one);
+  Fr zf = one, zi = one;
+  for (int e = 0; e < 5; ++e) { put(129 + e, zf); put(134 + e, zi); put(139 + e, zi * minv); zf = zf * zeta; zi = zi * zeta_inv; }
+  put(144, minv); put(145, two12); put(146, zinv * two12_inv); put(147, zinv);
+  HIP_TRY(hipMalloc(&d->stage, stage.size() * 8));
+  uint32_t* d_stage = d->stage;
+  HIP_TRY(hipMemcpy(d_stage, stage.data(), stage.size() * 8, hipMemcpyHostToDevice));
+  uint32_t** tables[4] = {&d->x_fwd, &d->x_inv, &d->xcos_fwd, &d->xcos_inv};
+  for (auto t : tables) HIP_TRY(hipMalloc(t, m * FPS_WORDS * 4));
+  HIP_TRY(hipMalloc(&d->xconsts, 15 * FPS_WORDS * 4));
+  HIP_TRY(hipMalloc(&d->consts, 4 * FPS_WORDS * 4));
+  HIP_TRY(hipMalloc(&d->work, m * 96));
+  const int nbits = ceil_log2(m);
+  for (int t = 0; t < 4; ++t)
+    hipLaunchKernelGGL((k_pow_table<M>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, *tables[t], d_stage + (size_t)t * 32 * 24,
+                       d_stage + (size_t)128 * 24, m, nbits);
+  hipLaunchKernelGGL((k_consts_to_internal<M>), dim3(1), dim3(64), 0, 0, d->xconsts, d_stage + (size_t)129 * 24, 15);
+  hipLaunchKernelGGL((k_consts_to_internal<M>), dim3(1), dim3(64), 0, 0, d->consts, d_stage + (size_t)144 * 24, 4);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  return 0;
+}
+
+// m = 2^a 5^b with a <= s and 1 <= b <= 2 on MNT6753 (the callers have checked)
+int create_mixed(int curve, int frm, size_t m, mnt753_domain** out) {
+  mnt753_domain* d = new (std::nothrow) mnt753_domain();
+  if (!d) return set_error(MNT753_ENOMEM, "domain_create_mixed: host allocation failed");
+  d->curve = curve; d->frm = frm; d->m = m; d->kind = MNT753_DOMAIN_MIXED;
+  d->q_n = 1; d->t_n = m;
+  while (d->t_n % 5 == 0) { d->t_n /= 5; d->q_n *= 5; ++d->q_pow; }
+  d->device = current_physical_device(); d->logical_device = mnt753_get_device();
+  OnDevice on(d->device);
+  int rc = 0;
+  if (d->t_n > 1) rc = create_basic(curve, frm, d->t_n, true, &d->sub_big);      // omega^q_n is that domain's own root
+  if (!rc) rc = build_mixed<MOD_B>(d);
+  if (rc) { mnt753_domain_free(d); return rc; }
+  *out = d;
+  return 0;
+}
+
 // ---- which domain libfqfft's get_evaluation_domain(min_size) builds (get_evaluation_domain.tcc:58-135) -----------------------------
 // Each candidate is accepted by its constructor's own test.  MNT6753's Fr has a small subgroup of order 5^2 defined
 // (mnt6753_init.cpp:73-75): there basic_radix2_domain accepts every 2^a 5^b, a <= 15, b <= 2, and get_root_of_unity likewise.
-// A candidate the reference accepts and this library does not build ends the walk with MNT753_EDOMAIN.
+// A candidate the reference accepts and this library does not build ends the walk with MNT753_EDOMAIN.  The mixed-radix basic
+// domains (candidates 1, 4 and 7 at a size 2^a 5^b, b >= 1) are built where the caller allows them (MNT753_DOMAIN_ALLOW_MIXED).
 struct Pick { int kind; size_t m; };           // kind < 0: refused, the message is set
 constexpr int Q_BASE = 5, Q_POWER = 2;         // MNT6753 Fr: small_subgroup_base, small_subgroup_power
 bool small_subgroup(int frm) { return frm == MOD_B; }
@@ -433,7 +544,8 @@ Pick refuse(const char* curve_name, size_t min_size, const char* fmt, size_t a) 
   set_error(MNT753_EDOMAIN, msg);
   return Pick{-1, 0};
 }
-Pick select_domain(int frm, size_t min_size) {
+Pick select_domain(int frm, size_t min_size, unsigned flags) {
+  const bool allow_mixed = flags & MNT753_DOMAIN_ALLOW_MIXED;
   const char* name = frm == MOD_A ? "MNT4753" : "MNT6753";
   if (min_size <= 1) {
     set_error(MNT753_EDOMAIN, "domain_create_for: min_size must be above 1 (no domain of the reference accepts 0 or 1)");
@@ -446,6 +558,7 @@ Pick select_domain(int frm, size_t min_size) {
     const size_t m = sizes[pass];
     if (basic_accepts(frm, m)) {
       if (is_pow2(m)) return Pick{MNT753_DOMAIN_BASIC, m};
+      if (allow_mixed) return Pick{MNT753_DOMAIN_MIXED, m};
       return refuse(name, min_size, "a mixed-radix basic_radix2_domain of size %zu (2^a 5^b)", m);
     }
     if (extended_accepts(frm, m)) {
@@ -465,6 +578,7 @@ Pick select_domain(int frm, size_t min_size) {
     }
     if (best != SIZE_MAX && basic_accepts(frm, best)) {
       if (is_pow2(best)) return Pick{MNT753_DOMAIN_BASIC, best};
+      if (allow_mixed) return Pick{MNT753_DOMAIN_MIXED, best};
       return refuse(name, min_size, "a mixed-radix basic_radix2_domain of size %zu (2^a 5^b, candidate 7)", best);
     }
   }
@@ -487,14 +601,31 @@ int mnt753_domain_create(int curve, size_t m, mnt753_domain** out) {
   return create_basic(curve, frm, m, false, out);
 }
 
-int mnt753_domain_create_for(int curve, size_t min_size, mnt753_domain** out) {
-  if (!out || curve < 0 || curve > 1) return set_error(MNT753_EINVAL, "domain_create_for: bad argument");
+int mnt753_domain_create_mixed(int curve, size_t m, mnt753_domain** out) {
+  if (!out || curve < 0 || curve > 1) return set_error(MNT753_EINVAL, "domain_create_mixed: bad argument");
   if (int rc = require_device()) return rc;
   const int frm = curve == MNT753_CURVE_MNT4753 ? MOD_A : MOD_B;
-  const Pick p = select_domain(frm, min_size);
+  // basic_radix2_domain over a field with a small subgroup (basic_radix2_domain.tcc:26-60); the powers of two are mnt753_domain_create's
+  int a, b; size_t rest;
+  split_2q(m ? m : 1, a, b, rest);
+  if (!small_subgroup(frm) || rest != 1 || b < 1 || b > Q_POWER || a > FRD[frm].two_adicity)
+    return set_error(MNT753_EDOMAIN, "domain_create_mixed: MNT6753 only, size must be 2^a 5^b with a <= 15 and 1 <= b <= 2");
+  return create_mixed(curve, frm, m, out);
+}
+
+int mnt753_domain_create_for_ex(int curve, size_t min_size, unsigned flags, mnt753_domain** out) {
+  if (!out || curve < 0 || curve > 1 || (flags & ~MNT753_DOMAIN_ALLOW_MIXED)) return set_error(MNT753_EINVAL, "domain_create_for: bad argument");
+  if (int rc = require_device()) return rc;
+  const int frm = curve == MNT753_CURVE_MNT4753 ? MOD_A : MOD_B;
+  const Pick p = select_domain(frm, min_size, flags);
   if (p.kind < 0) return MNT753_EDOMAIN;
   if (p.kind == MNT753_DOMAIN_BASIC) return create_basic(curve, frm, p.m, false, out);
+  if (p.kind == MNT753_DOMAIN_MIXED) return create_mixed(curve, frm, p.m, out);
   return create_outer(curve, frm, p.kind, p.m, out);
+}
+
+int mnt753_domain_create_for(int curve, size_t min_size, mnt753_domain** out) {
+  return mnt753_domain_create_for_ex(curve, min_size, 0, out);
 }
 
 int mnt753_domain_kind(const mnt753_domain* d) { return d ? d->kind : -1; }
@@ -545,7 +676,7 @@ int mnt753_divide_by_z_on_coset(mnt753_domain* d, uint64_t* dev_vec, void* strea
   const unsigned gb = (unsigned)((d->m + 255) / 256);
   uint32_t* v = reinterpret_cast<uint32_t*>(dev_vec);
   OnDevice on(d->device);
-  if (d->kind != MNT753_DOMAIN_BASIC) {
+  if (d->kind == MNT753_DOMAIN_STEP || d->kind == MNT753_DOMAIN_EXTENDED) {
     if (d->frm == MOD_A) hipLaunchKernelGGL((k_vec_mul_ztab<MOD_A>), dim3(gb), dim3(256), 0, (hipStream_t)stream, v, d->zt, d->z_split, d->z_mask, d->m);
     else hipLaunchKernelGGL((k_vec_mul_ztab<MOD_B>), dim3(gb), dim3(256), 0, (hipStream_t)stream, v, d->zt, d->z_split, d->z_mask, d->m);
   } else if (d->frm == MOD_A) hipLaunchKernelGGL((k_vec_mul_const<MOD_A>), dim3(gb), dim3(256), 0, (hipStream_t)stream, v, d->consts + 3 * FPS_WORDS, d->m);

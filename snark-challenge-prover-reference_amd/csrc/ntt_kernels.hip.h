@@ -534,6 +534,79 @@ __global__ void __launch_bounds__(256) k_h_pointwise_ztab(uint32_t* __restrict__
   store_wire_fp(a + i * 24, d);
 }
 
+// ---- mixed-radix domains m = Q T, Q = 5^b, T = 2^a (MNT6753: libfqfft basic_radix2_domain over the small subgroup of Fr,
+// basic_radix2_domain_aux.tcc:46-165 _basic_serial_mixed_radix_FFT) ------------------------------------------------------------------
+// Decimation in time over the radix-5 digits of the index:  x[i1 + Q i2]  ->  Q radix-2 transforms of size T over i2 (k_ntt_group,
+// unchanged, root omega^Q)  ->  b radix-5 levels that merge five neighbouring sub-transforms of width W = T (and 5T for Q = 25) each:
+//   X[base + W k1 + j] = sum_{l < 5} zeta^(k1 l) omega_W^(l j) Y[base + W l + j],   omega_W = omega^(m / 5W),  zeta = omega^(m / 5)
+// k_mixed_pre puts sub-vector i1 at slot s(i1) (i1 itself for Q = 5, its two base-5 digits swapped for Q = 25: the order the two
+// levels need), out of place; a level is in place: each butterfly reads and writes the same five positions.
+
+constexpr int R5_COLS = 64;                   // butterflies (columns) per block: one wave per row of the butterfly
+constexpr int R5_BLOCK = 5 * R5_COLS;
+
+// out[slot(i % Q) T + i / Q] = a[i] (* g^i: cosetFFT).  One lane per source element: reads and the coset table are coalesced.
+template <int M, bool COSET>
+__global__ void __launch_bounds__(256) k_mixed_pre(const uint32_t* __restrict__ a, uint32_t* __restrict__ out,
+                                                  const uint32_t* __restrict__ cos, size_t m, unsigned q_n, size_t t_n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const unsigned i1 = (unsigned)(i % q_n);
+  const size_t i2 = i / q_n;
+  const unsigned slot = q_n == 25 ? (i1 % 5) * 5 + i1 / 5 : i1;
+  uint32_t* dst = out + ((size_t)slot * t_n + i2) * 24;
+  if constexpr (COSET) {
+    Fp<M> x;
+    load_wire_fp(x, a + i * 24);
+    mul_table(x, cos + i * FPS_WORDS);
+    store_wire_fp(dst, x);
+  } else {
+    uint32_t w[24];
+    load_wire24(w, a + i * 24);
+    store_wire24(dst, w);
+  }
+}
+
+// One radix-5 level of width W, in place on `v` (m elements, wire form).  Five lanes per butterfly: wave l of a block holds row l of
+// 64 consecutive columns c = group * W + j (columns run on across the groups of 5W elements, so a width that is no multiple of 64 --
+// T = 1, 2, 8, 5T = 5, 10, 40 -- needs nothing special; a row's loads are coalesced wherever W >= 64).
+//   tw:  omega^k, k < m, device form (omega^-k for the inverse);  the lane's twiddle is entry l j tw_stride, tw_stride = m / 5W
+//   zc:  zeta^e, e < 5, device form (inverse, last level: zeta^-e / m -- the iFFT's scale rides on the constants; SCALED)
+//   out_scale (OUT_SCALE): table indexed by the output position, icosetFFT's g^-k on the last level
+// Ranges: a wire element is below p, the table entries below 2p; fp_mul and fp_add keep [0, 2p).
+template <int M, bool SCALED, bool OUT_SCALE>
+__global__ void __launch_bounds__(R5_BLOCK) k_radix5_merge(uint32_t* v, const uint32_t* __restrict__ tw, const uint32_t* __restrict__ zc,
+                                                          const uint32_t* __restrict__ out_scale, size_t n_cols, size_t width,
+                                                          size_t tw_stride) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[R5_BLOCK * FPS_WORDS];
+  const int row = threadIdx.x / R5_COLS, cc = threadIdx.x % R5_COLS;      // row is wave-uniform
+  const size_t c = (size_t)blockIdx.x * R5_COLS + cc;
+  const bool active = c < n_cols;
+  const size_t grp = c / width, j = c % width;
+  const size_t pos = grp * 5 * width + (size_t)row * width + j;           // < m wherever active
+  if (active) {
+    Fp<M> x;
+    load_wire_fp(x, v + pos * 24);
+    if (row != 0) mul_table(x, tw + (size_t)row * j * tw_stride * FPS_WORDS);
+    lds_store_fp(lds + (row * R5_COLS + cc) * FPS_WORDS, x);
+  }
+  __syncthreads();
+  if (!active) return;
+  Fp<M> acc, t, s;
+  lds_load_fp(acc, lds + cc * FPS_WORDS);
+  if constexpr (SCALED) mul_table(acc, zc);
+#pragma unroll 1
+  for (int l = 1; l < 5; ++l) {
+    const int e = (row * l) % 5;
+    lds_load_fp(t, lds + (l * R5_COLS + cc) * FPS_WORDS);
+    if (SCALED || e != 0) mul_table(t, zc + e * FPS_WORDS);
+    fp_add(s, acc, t);
+    acc = s;
+  }
+  if constexpr (OUT_SCALE) mul_table(acc, out_scale + pos * FPS_WORDS);
+  store_wire_fp(v + pos * 24, acc);
+}
+
 static __global__ void __launch_bounds__(256) k_copy_h(uint32_t* __restrict__ h, const uint32_t* __restrict__ a, size_t m) {
   // h[0..m) = a[0..m), h[m] = 0      (vector_Fr_zeros(m+1) + vector_Fr_copy_into, cuda_prover_piecewise.cu:50-51)
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // one thread per 16-byte quad

@@ -4,6 +4,7 @@
 // ./main_hip <curve> complete <keys> <input|witness> <challenge_proof> <full_proof> [--s-file <Fr> | --s-seed N]
 // ./main_hip <curve> check <params> [<input>] | check-r1cs <params> <r1cs> <witness>      (validation only; exit code 3 = malformed input)
 //            --validate on compute / compute-r1cs / complete: the same checks before proving; a failing job writes nothing
+//            --mixed-radix on compute / compute-r1cs / complete (or MNT753_MIXED_RADIX=1): MNT6753 domains of 2^a 5^b elements, up to 819200
 // Exit codes: 0 success, 1 device / I/O / self-test failure, 2 usage, 3 an input failed validation.
 //
 // The prover driver, same command line as the reference binaries (libsnark/main.cpp:274-293,
@@ -48,6 +49,9 @@ static int g_fold_rccl = -1;    // --fold rccl | host: where the partial points 
 // every job's input before its proof starts (scalars canonical, ca[i] cb[i] = cc[i] on every row -- for compute-r1cs that is the
 // witness against the system).  A failing job writes no output file; the process exits 3 if anything failed validation.
 static bool g_validate = false;
+// --mixed-radix (or MNT753_MIXED_RADIX=1): B::get_evaluation_domain also builds libfqfft's mixed-radix basic domains of MNT6753
+// (B::allow_mixed_radix); without it such a d + 1 ends with the library's message, as before
+static bool g_mixed_radix = false;
 struct validation_failed : std::runtime_error { using std::runtime_error::runtime_error; };
 
 // one line per set: "A: 1048577 points ok" / "H: 3 bad, first at 524288: off curve" / "constraint 17 of 30 is not satisfied"
@@ -241,6 +245,7 @@ template <typename B>
 int run_prover(const char* params_path, const std::vector<std::pair<std::string, std::string>>& jobs, const char* r1cs_path = nullptr) {
   if (g_gpus > 0) B::use_devices(g_gpus);
   B::fuse_C(g_fused_c);
+  B::allow_mixed_radix(g_mixed_radix);
   if (g_fold_rccl >= 0) B::fold_over_rccl(g_fold_rccl != 0);
   // The reference's CLI is a one-shot process: parameters loaded per invocation, one proof, exit (libsnark/main.cpp:196-203, :274-293).
   // Invoked the same way -- one job, no --repeat / --serve, one device -- this prover builds no window tables and runs no warm-up MSM:
@@ -418,14 +423,17 @@ int main(int argc, char** argv) {
     const char* s_file = nullptr; uint64_t s_seed = 0x73656564ull;
     bool validate = false;
     if (const char* e = getenv("MNT753_VALIDATE")) validate = atoi(e) != 0;
+    if (const char* e = getenv("MNT753_MIXED_RADIX")) g_mixed_radix = atoi(e) != 0;
     for (int i = 7; i < argc; ++i) {
       if (!strcmp(argv[i], "--validate")) { validate = true; continue; }
+      if (!strcmp(argv[i], "--mixed-radix")) { g_mixed_radix = true; continue; }
       if (i + 1 >= argc) break;
       if (!strcmp(argv[i], "--s-file")) s_file = argv[i + 1];
       else if (!strcmp(argv[i], "--s-seed")) s_seed = strtoull(argv[i + 1], nullptr, 0);
       ++i;
     }
     try {
+      mnt6753_hip::allow_mixed_radix(g_mixed_radix);
       if (validate) { if (int rc = validate_completion(curve, argv[3], argv[4], argv[5])) return rc; }
       return complete_proof(curve, argv[3], argv[4], argv[5], argv[6], s_file, s_seed);
     }
@@ -464,8 +472,9 @@ int main(int argc, char** argv) {
     }
   }
   if (const char* e = getenv("MNT753_VALIDATE")) g_validate = atoi(e) != 0;
+  if (const char* e = getenv("MNT753_MIXED_RADIX")) g_mixed_radix = atoi(e) != 0;
   if (argc < 6) {
-    fprintf(stderr, "usage: %s MNT4753|MNT6753 compute <params> <input> <output> [<input2> <output2> ...] [--repeat N] [--serve] [--gpus N] [--tables | --one-shot] [--unfused-h] [--unfused-c] [--ref-order] [--fold rccl|host] [--quiet]\n"
+    fprintf(stderr, "usage: %s MNT4753|MNT6753 compute <params> <input> <output> [<input2> <output2> ...] [--repeat N] [--serve] [--gpus N] [--tables | --one-shot] [--unfused-h] [--unfused-c] [--ref-order] [--fold rccl|host] [--validate] [--mixed-radix] [--quiet]\n"
                     "  further (input, output) pairs and --repeat prove against the parameters that are already resident on the GPU\n", argv[0]);
     return 2;
   }
@@ -496,6 +505,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--tables")) g_one_shot = 0;      // build the window tables even for a single proof
     else if (!strcmp(argv[i], "--one-shot")) g_one_shot = 1;    // no window tables, no warm-up MSM, whatever the job list
     else if (!strcmp(argv[i], "--validate")) g_validate = true;
+    else if (!strcmp(argv[i], "--mixed-radix")) g_mixed_radix = true;
     else {
       // an option this prover does not have (or one that lost its argument), or an input without its output: refuse, do not guess
       fprintf(stderr, argv[i][0] == '-' ? "main_hip: unknown option %s\n" : "main_hip: input %s without an output path\n", argv[i]);

@@ -16,6 +16,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <thread>
+#include <tuple>
 #include <string>
 #include <vector>
 
@@ -136,6 +137,8 @@ static bool one_shot_mode() {
   if (const char* e = getenv("MNT753_ONE_SHOT")) return atoi(e) != 0;
   return g_one_shot != 0;
 }
+// B::allow_mixed_radix(true): get_evaluation_domain passes MNT753_DOMAIN_ALLOW_MIXED (the library takes it per call and keeps no switch)
+static unsigned g_domain_flags = 0;
 // contiguous slice g of n elements over n_dev devices (multiexp.tcc:417-431: one = n / chunks, the last slice takes the remainder)
 static void slice_bounds(size_t n, int n_dev, int g, size_t* lo, size_t* hi) {
   const size_t one = n / (size_t)n_dev;
@@ -688,21 +691,22 @@ template <int CURVE> void HIP_B::print_G2(G2* a) {
 // creates the domain for d + 1 ahead of time -- it depends on the parameters only, like the MSM window tables.
 template <int CURVE> static std::shared_ptr<DomainHolder> cached_domain(size_t d, int device = 0) {
   static std::mutex mu;
-  static std::map<std::pair<int, size_t>, std::shared_ptr<DomainHolder>> cache;
+  static std::map<std::tuple<int, size_t, unsigned>, std::shared_ptr<DomainHolder>> cache;
   std::lock_guard<std::mutex> l(mu);
-  auto it = cache.find({device, d});
+  const unsigned flags = g_domain_flags;
+  auto it = cache.find({device, d, flags});
   if (it != cache.end()) return it->second;
   auto h = std::make_shared<DomainHolder>();
   {
     DeviceScope on(device);   // a domain lives on the device that is current when it is created
-    check(mnt753_domain_create_for(CURVE, d, &h->h), "mnt753_domain_create_for");
+    check(mnt753_domain_create_for_ex(CURVE, d, flags, &h->h), "mnt753_domain_create_for");
   }
-  // libfqfft's get_evaluation_domain may round a size up (big + rounded_small).  The reference prover then throws from iFFT, whose
+  // libfqfft's get_evaluation_domain may round a size up (big + rounded_small, or the mixed-radix best fit of candidate 7).  The reference prover then throws from iFFT, whose
   // vectors have d + 1 elements and not m: no proof exists for such parameters, and none is written here either
   if (const size_t m = mnt753_domain_size(h->h); m != d)
     throw std::runtime_error("the evaluation domain for d + 1 = " + std::to_string(d) + " has " + std::to_string(m) +
                              " elements: the reference's iFFT refuses vectors of another size than the domain's (a.size() != m), there is no proof for these parameters");
-  cache[{device, d}] = h;
+  cache[{device, d, flags}] = h;
   return h;
 }
 template <int CURVE> typename HIP_B::evaluation_domain* HIP_B::get_evaluation_domain(size_t d) {
@@ -1075,6 +1079,7 @@ template <int CURVE> typename HIP_B::G1* HIP_B::groth16_C(groth16_params* p, vec
 template <int CURVE> void HIP_B::fuse_C(bool on) { g_fused_c = on ? 1 : 0; }
 template <int CURVE> void HIP_B::fold_over_rccl(bool on) { g_fold_rccl = on ? 1 : 0; }
 template <int CURVE> void HIP_B::one_shot(bool on) { g_one_shot = on ? 1 : 0; }
+template <int CURVE> void HIP_B::allow_mixed_radix(bool on) { g_domain_flags = on ? MNT753_DOMAIN_ALLOW_MIXED : 0u; }
 
 template <int CURVE> typename HIP_B::groth16_input* HIP_B::read_input(const char* path, groth16_params* params) {
   return new groth16_input(path, params->d, params->m);

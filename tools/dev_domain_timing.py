@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Development timing (GPU box): compute_H per evaluation domain, HIP events on the default stream, 5 warm-up + 20 timed calls.
 
-    python tools/dev_domain_timing.py [--lib PATH/libmnt753_hip.so] CASE [CASE ...]       CASE = MNT4753:1048576, MNT6753:65536, ...
+    python tools/dev_domain_timing.py [--lib PATH/libmnt753_hip.so] CASE [CASE ...]       CASE = MNT4753:1048576, MNT6753:65536, MNT6753:163840, ...
 
 Plain ctypes on the library named by --lib (default: the one in the package directory), so that an OLDER build -- one without
 mnt753_domain_create_for -- can be timed on its power-of-two sizes for an A/B comparison on one box: run the two builds alternately,
@@ -48,6 +48,9 @@ def main():
 
     create = getattr(L, "mnt753_domain_create_for", None) or L.mnt753_domain_create     # an older build: power-of-two sizes only
     create.argtypes = [C.c_int, sz, C.POINTER(vp)]
+    if hasattr(L, "mnt753_domain_create_for_ex"):      # mixed-radix sizes of MNT6753 (5 * 2^15, 25 * 2^15) allowed; the others select as before
+        L.mnt753_domain_create_for_ex.argtypes = [C.c_int, sz, C.c_uint, C.POINTER(vp)]
+        create = lambda curve, m, out: L.mnt753_domain_create_for_ex(curve, m, 1, out)
     ok(L.mnt753_init(0), "mnt753_init")
     ev = [vp(), vp()]
     for e in ev:

@@ -148,6 +148,14 @@ int mnt753_domain_create_for(int curve, size_t min_size, mnt753_domain** out) {
   if (min_size <= 1) return fail(MNT753_EDOMAIN, "domain_create_for: min_size must be above 1");
   *out = new mnt753_domain{curve, min_size, t_dev}; return 0;
 }
+int mnt753_domain_create_for_ex(int curve, size_t min_size, unsigned flags, mnt753_domain** out) {
+  if (flags & ~MNT753_DOMAIN_ALLOW_MIXED) return fail(MNT753_EINVAL, "domain_create_for: bad argument");
+  return mnt753_domain_create_for(curve, min_size, out);
+}
+int mnt753_domain_create_mixed(int curve, size_t m, mnt753_domain** out) {
+  if (!out || curve != MNT753_CURVE_MNT6753 || m <= 1 || m % 5) return fail(MNT753_EDOMAIN, "domain_create_mixed: not 2^a 5^b on MNT6753");
+  *out = new mnt753_domain{curve, m, t_dev}; return 0;
+}
 int mnt753_domain_kind(const mnt753_domain* d) { return !d ? -1 : (d->m & (d->m - 1)) ? MNT753_DOMAIN_STEP : MNT753_DOMAIN_BASIC; }
 int mnt753_domain_free(mnt753_domain* d) { delete d; return 0; }
 size_t mnt753_domain_size(const mnt753_domain* d) { return d ? d->m : 0; }
