@@ -15,6 +15,7 @@
 #include "host_field.hpp"
 #include "msm_kernels.hip.h"
 #include "msm_knobs.hpp"
+#include "msm_limits.hpp"
 #include "msm_types.hpp"
 #include "msm_sort.hpp"
 #include "mnt753_generators.h"
@@ -214,13 +215,16 @@ int bases_create_t(mnt753_bases* b, const uint64_t* affine, int on_device, size_
     pW = (754 + pc - 1) / pc;
     if ((uint64_t)pW * n >= 0x7fffffffull) { want_table = false; pc = 0; pW = 1; }   // row index must fit 31 bits
   }
-  if (hipMalloc(&b->d_aff, sizeof(uint32_t) * aff_words<C>() * std::max<size_t>(n, 1) * (size_t)pW) != hipSuccess) {
-    // no room for the window table (8.9 GB per 2^20 G1 points, 26 GB for Fq3): keep the set usable with one bucket set per window
+  // rows of row_words (base fields: 256 B, x and y on 128-byte lines of their own; hipMalloc aligns the base address)
+  if (hipMalloc(&b->d_aff, sizeof(uint32_t) * row_words<C>() * std::max<size_t>(n, 1) * (size_t)pW) != hipSuccess) {
+    // no room for the window table (10.7 GB per 2^20 G1 points, 26 GB for Fq3): keep the set usable with one bucket set per window
     (void)hipGetLastError();
     if (!want_table) return set_error(MNT753_ENOMEM, "bases_create: device allocation failed");
     want_table = false; pc = 0; pW = 1;
-    HIP_TRY(hipMalloc(&b->d_aff, sizeof(uint32_t) * aff_words<C>() * std::max<size_t>(n, 1)));
+    HIP_TRY(hipMalloc(&b->d_aff, sizeof(uint32_t) * row_words<C>() * std::max<size_t>(n, 1)));
   }
+  // the padding of the rows is written once, as zero (so are the rows of identity bases, which the table builder skips)
+  if (row_words<C>() != aff_words<C>()) HIP_TRY(hipMemsetAsync(b->d_aff, 0, sizeof(uint32_t) * row_words<C>() * std::max<size_t>(n, 1) * (size_t)pW, 0));
   HIP_TRY(hipMalloc(&b->d_inf, std::max<size_t>(n, 1)));
   if (n == 0) return 0;
   const uint32_t* src = reinterpret_cast<const uint32_t*>(affine);
@@ -230,7 +234,7 @@ int bases_create_t(mnt753_bases* b, const uint64_t* affine, int on_device, size_
     HIP_TRY(hipMemcpy(staged, affine, wire_bytes, hipMemcpyHostToDevice));
     src = staged;
   }
-  hipLaunchKernelGGL((k_bases_to_internal<C>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, src, b->d_aff, b->d_inf, n);
+  hipLaunchKernelGGL((k_bases_to_internal<C, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, src, b->d_aff, b->d_inf, n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   if (staged) HIP_TRY(hipFree(staged));
@@ -433,9 +437,10 @@ MsmPlan plan_for(const mnt753_bases* b, size_t n, const MsmKnobs& knobs) {
   p.pair_levels = b->no_pair ? 0 : pair_levels<PointCfg<C>>((uint64_t)p.W * n, b, knobs);
   // the padded list must keep 32-bit slot indices
   while (p.pair_levels > 0 && (uint64_t)p.W * n + (uint64_t)p.n_buckets * (((uint64_t)1 << p.pair_levels) - 1) >= 0xfffffff0ull) --p.pair_levels;
-  // base fields: the first level keeps table offsets in 32-bit registers (uint4 units, 14 per row) -- a table of 64 GiB or more
-  // (2^23 G1 points with 38 windows) goes through the accumulate kernel alone
-  if (point_lanes<C>() == 1 && C::F::DEG == 1 && (uint64_t)p.W * std::max<uint64_t>(b->n, n) * 14u >= 0xffffffffull) p.pair_levels = 0;
+  // base fields: the first level keeps table offsets in 32-bit registers (uint4 units, 16 per 256-byte row) -- a table of 64 GiB or
+  // more, 2^28 rows (2^23 G1 points with 35 windows; H | L | B1, 3 * 2^20 points with 36, has 0.42 * 2^28) goes through the accumulate
+  // kernel alone
+  if (point_lanes<C>() == 1 && C::F::DEG == 1 && !pair_row_offsets_fit((uint64_t)p.W * std::max<uint64_t>(b->n, n), row_words<C>() / 4)) p.pair_levels = 0;
   // every field: blocked indices of level-1 slots (7 uint4 per element and lane) are 32-bit in the level kernels
   if (p.pair_levels > 0 && pair_cap1(p, n) * (uint64_t)point_lanes<C>() * 7u >= 0xffffff00ull) p.pair_levels = 0;
   p.irr_levels = p.pair_levels > 0 ? irr_levels_for<PointCfg<C>>((uint64_t)p.W * n, p.pair_levels, p.n_buckets, b, knobs) : 0;
@@ -679,7 +684,7 @@ int msm_start_t(mnt753_bases* b, size_t base_offset, const uint64_t* scalars, in
     d_scal = reinterpret_cast<const uint32_t*>(b->d_scalars_stage);
   }
   // with the window table the sorted entries carry absolute table rows (w * n_total + base_offset + i)
-  const uint32_t* d_aff = p.pre ? b->d_aff : b->d_aff + base_offset * aff_words<C>();
+  const uint32_t* d_aff = p.pre ? b->d_aff : b->d_aff + base_offset * row_words<C>();
   const uint8_t* d_inf = b->d_inf + base_offset;
   HIP_TRY(hipEventRecord(b->ev[0], st));
   if (b->d_part_ws && sort_mode((uint64_t)p.W * n, knobs) == SORT_PART && msm_sort_partition_fits(p.n_buckets, p.W)) {

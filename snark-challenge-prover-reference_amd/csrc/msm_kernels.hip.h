@@ -147,6 +147,22 @@ __device__ __forceinline__ void e_store(uint32_t* p, const typename F::E& a) {
 }
 template <class C>
 constexpr int aff_words() { return 2 * C::F::DEG * FPS_WORDS; }
+// Rows of a base set's d_aff (plain bases and window table alike) have a stride of their own.  The fabric moves 128-byte lines, and a
+// 224-byte row at a 224-byte stride starts at offset 0 / 96 / 64 / 32 of a line: the x read of level 1's forward sweep (112 B) then
+// touches 1.75 lines on average and the whole-row read of its backward sweep 2.5, 544 B fetched for 336 B used.  Base-field rows are
+// therefore padded to 256 B with y on a line of its own -- x in words 0..27, y in words 32..59, the rest zero: one line for x, two for
+// the row.  The lane-split fields keep packed rows unless MNT753_ROW_PAD_EXT is set (their 448- / 672-byte rows take
+// four / six lines either way, only the x read would shrink, for a table 14 % larger: DESIGN.md 4.3).  Every other affine array (level planes,
+// d_gen, wire conversion) stays aff_words.
+#ifndef MNT753_ROW_PAD_EXT
+#define MNT753_ROW_PAD_EXT 0
+#endif
+template <class C>
+constexpr bool row_padded() { return C::F::DEG == 1 || MNT753_ROW_PAD_EXT; }
+template <class C>
+constexpr int row_y_off() { return row_padded<C>() ? (C::F::DEG * FPS_WORDS + 31) / 32 * 32 : C::F::DEG * FPS_WORDS; }   // words from x to y
+template <class C>
+constexpr int row_words() { return 2 * row_y_off<C>(); }
 template <class C>
 constexpr int proj_words() { return 3 * C::F::DEG * FPS_WORDS; }
 template <class C>
@@ -182,14 +198,16 @@ __device__ __forceinline__ void store_wire24(uint32_t* p, const uint32_t w[24]) 
 // ---- base conversion ------------------------------------------------------------------------
 // wire affine (x then y, each DEG x 12 u64 little-endian Montgomery R=2^768; y == 0 encodes the
 // identity, libsnark/serialization.hpp:84-111) -> device affine + identity flag
-template <class C>
+// ROWS: `out` is a base set's d_aff (rows of row_words, y at row_y_off; the padding is zeroed by the caller); otherwise packed affine
+template <class C, bool ROWS = false>
 __global__ void __launch_bounds__(256) k_bases_to_internal(const uint32_t* __restrict__ wire, uint32_t* __restrict__ out,
                                                           uint8_t* __restrict__ inf, size_t n) {
   using F = typename C::F;
+  constexpr int YPAD = ROWS ? row_y_off<C>() - F::DEG * FPS_WORDS : 0;   // padding words between x and y
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t* src = wire + i * 2 * wire_coord_words<C>();
-  uint32_t* dst = out + i * aff_words<C>();
+  uint32_t* dst = out + i * (ROWS ? row_words<C>() : aff_words<C>());
   uint32_t yor = 0;
 #pragma unroll 1
   for (int k = 0; k < 2 * F::DEG; ++k) {
@@ -201,7 +219,7 @@ __global__ void __launch_bounds__(256) k_bases_to_internal(const uint32_t* __res
     }
     Fp<F::MOD> v;
     fp_from_wire(v, w);
-    fp_store(dst + k * FPS_WORDS, v);
+    fp_store(dst + k * FPS_WORDS + (k >= F::DEG ? YPAD : 0), v);
   }
   inf[i] = (yor == 0) ? 1 : 0;
 }
@@ -522,9 +540,9 @@ __global__ void __launch_bounds__(256, vm_waves<C>()) k_bucket_accumulate(const 
       }
     } else {
       s = sorted[e];
-      const uint32_t* src = bases + (size_t)(s & 0x7fffffffu) * aff_words<C>();
+      const uint32_t* src = bases + (size_t)(s & 0x7fffffffu) * row_words<C>();   // a row of d_aff
       e_load<F>(Q.X, src);
-      e_load<F>(Q.Y, src + F::DEG * FPS_WORDS);
+      e_load<F>(Q.Y, src + row_y_off<C>());
     }
     if (s & 0x80000000u) F::neg(Q.Y, Q.Y);
     int pc = PC_MADD;
@@ -587,7 +605,7 @@ __global__ void __launch_bounds__(256, vm_waves<C>()) k_bucket_accumulate(const 
 //   * rows handed to the NEXT pairing level: four planes (x | y) x (even | odd slot), j = (slot / 2) * LANES + component --
 //     the reader's slot o' takes x1, y1 from the even planes and x2, y2 from the odd planes at j = o' * LANES + component,
 //     the writer's lanes alternate between the two planes and still fill whole 64-byte sectors.
-// Only level 1's input stays row-major (224-byte rows of the window table, gathered row-cooperatively); the accumulate kernel
+// Only level 1's input stays row-major (rows of the window table, row_words: 256 bytes on a base field, gathered row-cooperatively); the accumulate kernel
 // reads the last level's planes (a row-major last level cost 1.2 ms at 2^20 in 64-partial-sector stores).
 // Side paths: an odd leftover is copied with its sign flag; equal points are doubled (denominator 2y); opposite points
 // cancel: the slot gets the fixed point D (`gen`, the group generator) and fix_count[bucket] is incremented -- k_pair_fix
@@ -827,11 +845,15 @@ __global__ void __launch_bounds__(256, MNT753_PAIR_WAVES) k_pair_level(const uin
   using E = typename F::E;                 // a single Fp: base field, or one component per lane of a lane-split field
   constexpr int M = F::MOD;
   constexpr int EW = F::DEG * FPS_WORDS;   // storage words of one element (row-major rows)
-  constexpr int AW = aff_words<C>();
+  constexpr int TW = row_words<C>(), TY = row_y_off<C>();   // words of a table row (first level), and from its x to its y
   constexpr uint32_t LN = F::LANES;
   constexpr uint32_t NS = 64u / LN;                       // slots of a wave (21 for three lanes per point)
   constexpr uint32_t RQ = 14u * F::DEG;                   // quads of a table row (x | y)
   constexpr uint32_t XQ = 7u * F::DEG;                    // quads of its x coordinate
+  // the row in memory (row_words): TQ quads from row to row, YPQ quads of padding between x and y.  The LDS image stays packed, RQ
+  // quads per row: piece q of a row sits at quad q of the table row, behind the padding once it belongs to y -- the padding is
+  // never fetched, and the number of DMA instructions per slot is what it was
+  constexpr uint32_t TQ = (uint32_t)TW / 4u, YPQ = (uint32_t)TY / 4u - XQ;
   static_assert(2 * NS * RQ <= PAIR_IMG_QUADS, "row image");
   // first level of a base field: the table offsets of the next slot's pieces are read out of the entry image ahead of the
   // loads (per portion).  The lane-split fields keep a ds_read in front of every piece: their multiplier leaves no registers.
@@ -911,7 +933,7 @@ __global__ void __launch_bounds__(256, MNT753_PAIR_WAVES) k_pair_level(const uin
       const uint32_t p = rs >= NS ? 1u : 0u, s = rs - p * NS;
       const uint32_t e = ent_img[buf * 128u + 2u * s + p];
       const uint32_t r = e == ENTRY_EMPTY ? 0u : PAIR_ROW(e & 0x7fffffffu);
-      glds16(table + (size_t)r * RQ + q, im + 64u * k);
+      glds16(table + (size_t)r * TQ + q + (!xonly && q >= XQ ? YPQ : 0u), im + 64u * k);
     } else {
       const uint32_t o = min(it * NLe + (lane_on ? t : t0w), S - 1u);
       const uint32_t j = o * LN + comp;
@@ -934,7 +956,7 @@ __global__ void __launch_bounds__(256, MNT753_PAIR_WAVES) k_pair_level(const uin
     const uint32_t rs = i / RQ, q = i - rs * RQ;
     const uint32_t p = rs >= NS ? 1u : 0u, s = rs - p * NS;
     const uint32_t e = ent_img[buf * 128u + 2u * s + p];
-    return (e == ENTRY_EMPTY ? 0u : PAIR_ROW(e & 0x7fffffffu)) * RQ + q;
+    return (e == ENTRY_EMPTY ? 0u : PAIR_ROW(e & 0x7fffffffu)) * TQ + q + (q >= XQ ? YPQ : 0u);
   };
   auto load_row_offsets = [=](uint32_t buf, auto xonly_c, uint32_t (&off)[ROW_PIECES]) __attribute__((always_inline)) {
     constexpr bool xonly = decltype(xonly_c)::value;
@@ -948,7 +970,7 @@ __global__ void __launch_bounds__(256, MNT753_PAIR_WAVES) k_pair_level(const uin
       const uint32_t p = rs >= NS ? 1u : 0u, s = rs - p * NS;
       const uint32_t e = ent_img[buf * 128u + 2u * s + p];
       const uint32_t r = e == ENTRY_EMPTY ? 0u : PAIR_ROW(e & 0x7fffffffu);
-      off[k] = r * RQ + q;
+      off[k] = r * TQ + q + (!xonly && q >= XQ ? YPQ : 0u);
     }
   };
   // this thread's operands of the current slot, out of the image
@@ -1034,8 +1056,8 @@ __global__ void __launch_bounds__(256, MNT753_PAIR_WAVES) k_pair_level(const uin
         // same x: equal points (doubling, denominator 2y) or opposite points (cancellation, take 1).  Rare: plain loads.
         if constexpr (first) {
           const uint2 e = reinterpret_cast<const uint2*>(entries)[o];
-          fp_load(y1, src_rows + (size_t)PAIR_ROW(e.x & 0x7fffffffu) * AW + EW + cw);
-          fp_load(y2, src_rows + (size_t)PAIR_ROW(e.y & 0x7fffffffu) * AW + EW + cw);
+          fp_load(y1, src_rows + (size_t)PAIR_ROW(e.x & 0x7fffffffu) * TW + TY + cw);
+          fp_load(y2, src_rows + (size_t)PAIR_ROW(e.y & 0x7fffffffu) * TW + TY + cw);
         } else if constexpr (IRR) {
           const uint32_t s1 = sw_cur & 0x7fffffffu, s2 = s1 + 1u;
           (void)fp_load_blk(y1, src_planes + (2 + (s1 & 1u)) * src_stride, (s1 >> 1) * LN + comp);
@@ -1844,7 +1866,7 @@ __device__ void e_inv(Fp3E<M>& r, const Fp3E<M>& x, FieldFp3<M, NR>*) {   // fp3
 
 // (the doubling chain of the table runs in modified Jacobian coordinates: jac_dbl, curve753.hip.h)
 // One logical lane (1, 2 or 3 threads, msm_kernels' lane-split convention) per point of a tile [i0, i0 + count): table rows for
-// w >= 1; row 0 is the base itself (d_aff).   ztmp: [W][count] E  (Z_w),  ptmp: [W][count] E (prefix products of the Z_w)
+// w >= 1; row 0 is the base itself (d_aff); rows of row_words, y at row_y_off.   ztmp: [W][count] E  (Z_w),  ptmp: [W][count] E (prefix products of the Z_w)
 template <class C>
 __global__ void __launch_bounds__(256, 1) k_precompute_windows(uint32_t* __restrict__ table, const uint8_t* __restrict__ inf,
                                                               uint32_t* __restrict__ ztmp, uint32_t* __restrict__ ptmp, size_t n_total,
@@ -1858,8 +1880,8 @@ __global__ void __launch_bounds__(256, 1) k_precompute_windows(uint32_t* __restr
   const size_t i = i0 + t;
   if (inf[i]) return;   // identity bases never enter a bucket (their digits are forced to 0)
   Jac<F> R;
-  e_load<F>(R.X, table + i * aff_words<C>());
-  e_load<F>(R.Y, table + i * aff_words<C>() + EW);
+  e_load<F>(R.X, table + i * row_words<C>());
+  e_load<F>(R.Y, table + i * row_words<C>() + row_y_off<C>());
   F::one(R.Z);
   C::coeff_a(R.W);
   // pass 1: R_w = 2^c R_{w-1}; keep X, Y in the table row and Z in ztmp
@@ -1867,9 +1889,9 @@ __global__ void __launch_bounds__(256, 1) k_precompute_windows(uint32_t* __restr
   for (int w = 1; w < W; ++w) {
 #pragma unroll 1
     for (int k = 0; k < c; ++k) jac_dbl<C>(R);
-    uint32_t* row = table + ((size_t)w * n_total + i) * aff_words<C>();
+    uint32_t* row = table + ((size_t)w * n_total + i) * row_words<C>();
     e_store<F>(row, R.X);
-    e_store<F>(row + EW, R.Y);
+    e_store<F>(row + row_y_off<C>(), R.Y);
     e_store<F>(ztmp + ((size_t)w * count + t) * EW, R.Z);
   }
   // pass 2: batch inversion of Z_1..Z_{W-1} (Montgomery's trick) and normalisation to affine: x = X / Z^2, y = Y / Z^3
@@ -1887,9 +1909,9 @@ __global__ void __launch_bounds__(256, 1) k_precompute_windows(uint32_t* __restr
   for (int w = W - 1; w >= 1; --w) {
     e_load<F>(tmp, ptmp + ((size_t)w * count + t) * EW);
     e_load<F>(z, ztmp + ((size_t)w * count + t) * EW);
-    uint32_t* row = table + ((size_t)w * n_total + i) * aff_words<C>();
+    uint32_t* row = table + ((size_t)w * n_total + i) * row_words<C>();
     e_load<F>(x, row);
-    e_load<F>(y, row + EW);
+    e_load<F>(y, row + row_y_off<C>());
     // five products through one multiplier instance: 1 / Z_w, the running inverse, 1 / Z^2, x, 1 / Z^3, y
     E zi2;
 #pragma nounroll
@@ -1910,7 +1932,7 @@ __global__ void __launch_bounds__(256, 1) k_precompute_windows(uint32_t* __restr
         case 2: zi2 = r; break;
         case 3: e_store<F>(row, r); break;
         case 4: zi = r; break;
-        default: e_store<F>(row + EW, r); break;
+        default: e_store<F>(row + row_y_off<C>(), r); break;
       }
     }
   }

@@ -165,11 +165,12 @@ int run_acc(const char* name, const char* golden, uint32_t T, uint32_t REP = 1) 
     if (i == 0 || i >= 5) { wire.emplace_back(rec.begin(), rec.begin() + aw); if ((int)wire.size() < npts) wire.emplace_back(rec.begin() + aw, rec.begin() + 2 * aw); }
   }
   fclose(f);
-  std::vector<uint32_t> h_pts((size_t)npts * aff_words<C>(), 0);
+  // rows as k_bucket_accumulate gathers them: the layout of a base set's d_aff (row_words, y at row_y_off)
+  std::vector<uint32_t> h_pts((size_t)npts * row_words<C>(), 0);
   for (int i = 0; i < npts; ++i)
     for (int k = 0; k < 2 * F::DEG; ++k) {
       Fp<F::MOD> v; fp_from_wire(v, (const uint32_t*)(wire[i].data() + 12 * k));
-      memcpy(&h_pts[(size_t)i * aff_words<C>() + k * FPS_WORDS], v.l, NL * 4);
+      memcpy(&h_pts[(size_t)i * row_words<C>() + (k < F::DEG ? k * FPS_WORDS : row_y_off<C>() + (k - F::DEG) * FPS_WORDS)], v.l, NL * 4);
     }
   const int base_sizes[] = {1, 2, 3, 4, 5, 1, 0, 3, 7, 2, 6, 3, 0, 0, 9, 1};
   const uint32_t nb = 16 * REP;

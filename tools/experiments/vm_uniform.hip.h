@@ -244,9 +244,9 @@ __global__ void __launch_bounds__(256, vm_waves<C>()) k_bucket_accumulate_u(cons
     }
     if (live) {
       const uint32_t s = sorted[e];
-      const uint32_t* src = bases + (size_t)(s & 0x7fffffffu) * aff_words<C>();
+      const uint32_t* src = bases + (size_t)(s & 0x7fffffffu) * row_words<C>();   // a row of d_aff
       e_load<F>(qx, src);
-      e_load<F>(qy, src + EW);
+      e_load<F>(qy, src + row_y_off<C>());
       if (s & 0x80000000u) F::neg(qy, qy);
     }
     const bool start = live && (acc_zero || F::is_zero(acc.ZZ));   // empty accumulator, or a run that summed to the identity
