@@ -17,6 +17,11 @@ extern "C" {
  * at sizes no CPU implementation finishes quickly. */
 int mnt753_synth_points(int curve, int group, uint64_t seed, size_t n, uint64_t* out_affine, int threads);
 int mnt753_synth_expected_msm(int curve, int group, uint64_t seed, size_t n, const uint64_t* scalars, uint64_t* out_projective);
+/* The group generator G as the library holds it (the GEN_* words of csrc/mnt753_generators.h, affine wire form, mnt753_affine_words
+ * words; host only, no device needed).  It is also the stand-in point D of the batched-affine levels: a pair P, -P that cancels
+ * leaves D in its slot and k_pair_fix subtracts fix_count * D from the bucket afterwards, so a base set that holds G or -G itself
+ * meets D as an equal or an opposite point (tests/msm_occupancy.py, profile `collisions`). */
+int mnt753_test_generator(int curve, int group, uint64_t* out_affine);
 
 /* ---- test hooks (tests/ only; not used by the prover) -------------------------------------------------
  * The device field layer element-wise on n pairs of Fp elements in wire form (host pointers in and out), for known-answer

@@ -142,6 +142,7 @@ def test_lib():
     sig = {
         "mnt753_synth_points": (i, [i, i, C.c_uint64, sz, u64p, i]),
         "mnt753_synth_expected_msm": (i, [i, i, C.c_uint64, sz, u64p, u64p]),
+        "mnt753_test_generator": (i, [i, i, u64p]),
         "mnt753_test_field_op": (i, [i, i, u64p, u64p, sz, u64p]),
         "mnt753_test_ext_op": (i, [i, i, i, u64p, u64p, sz, u64p]),
         "mnt753_test_point_op": (i, [i, i, i, i, u64p, u64p, sz, u64p]),
@@ -450,6 +451,13 @@ def synth_expected_msm(curve, group, seed, scalars):
     return out
 
 
+def test_generator(curve, group):
+    """Test hook: the group generator in affine wire form -- the point the pairing levels write for a cancelled pair."""
+    out = np.zeros(affine_words(curve, group), dtype=np.uint64)
+    _check(test_lib().mnt753_test_generator(curve, group, out.ctypes.data_as(C.POINTER(C.c_uint64))), "mnt753_test_generator")
+    return out
+
+
 def _input_ptr(data, on_device, words, n):
     """-> (pointer, element count, array to keep alive) for a numpy array or, with on_device, a device address"""
     if on_device:
@@ -600,6 +608,7 @@ def test_point_op(curve, group, split, op, p, q=None):
     return out
 
 
+test_generator.__test__ = False
 test_field_raw.__test__ = False
 test_ext_raw.__test__ = False
 test_ext_op.__test__ = False

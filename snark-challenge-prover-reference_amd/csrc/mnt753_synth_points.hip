@@ -139,4 +139,11 @@ int mnt753_synth_expected_msm(int curve, int group, uint64_t seed, size_t n, con
   if (curve < 0 || curve > 1 || (group != MNT753_G1 && group != MNT753_G2) || !out_projective || (n && !scalars)) return set_error(MNT753_EINVAL, "synth_expected_msm: bad argument");
   return DISPATCH_CG(synth_expected_t, seed, n, scalars, out_projective);
 }
+// the GEN_* words of mnt753_generators.h as they stand: the point the pairing levels write for a cancelled pair (ensure_pair_ws, D)
+int mnt753_test_generator(int curve, int group, uint64_t* out_affine) {
+  if (curve < 0 || curve > 1 || (group != MNT753_G1 && group != MNT753_G2) || !out_affine) return set_error(MNT753_EINVAL, "test_generator: bad argument");
+  const uint64_t* w = curve == MNT753_CURVE_MNT4753 ? (group == MNT753_G1 ? GEN_MNT4_G1 : GEN_MNT4_G2) : (group == MNT753_G1 ? GEN_MNT6_G1 : GEN_MNT6_G2);
+  memcpy(out_affine, w, sizeof(uint64_t) * mnt753_affine_words(curve, group));
+  return 0;
+}
 }

@@ -489,6 +489,7 @@ int pair_and_accumulate(const MsmPlan& p, size_t n, hipStream_t st, const uint32
         if (c > room || c > b->pair_cap / 2 + b->pair_buckets + 64) { irr = k - 1; break; }   // rows of the level, source words
       }
     }
+    g_last_run.irr_levels = irr;   // the record of the last run says what ran, not what the plan asked for
     for (int l = 1; l <= levels; ++l) {
       cap /= 2;                                 // worst-case slots of this level (the kernel reads the actual count from offsG)
       const uint32_t lanes = (uint32_t)std::min<uint64_t>(max_lanes, (cap + min_B - 1) / min_B);
@@ -669,7 +670,7 @@ int msm_start_t(mnt753_bases* b, size_t base_offset, const uint64_t* scalars, in
     p = plan_for<C>(b, n, knobs);
   }
   if (int rc = ensure_ws<C>(b, n, p, knobs)) return rc;
-  // the plan is final: the record of the last run (the irregular levels the plan asks for, also where pair_and_accumulate has room for fewer)
+  // the plan is final: the record of the last run (pair_and_accumulate lowers irr_levels to what it has room for, if that is fewer)
   b->run_plan = p;
   g_last_run.plan[0] = p.c; g_last_run.plan[1] = p.W; g_last_run.plan[2] = p.pre; g_last_run.plan[3] = (int)p.T;
   g_last_run.pair_levels = p.pair_levels;
