@@ -194,6 +194,39 @@ int mnt753_point_to_affine(int curve, int group, const uint64_t* p_proj, uint64_
 /* read_g1 / read_g2 decoding (serialization.hpp:84-111): y == 0 -> identity */
 int mnt753_point_from_affine(int curve, int group, const uint64_t* affine, uint64_t* out_proj);
 
+/* ---- fixed-base batch scalar multiplication ---------------------------------------------------------------
+ * n scalars times ONE base point: libff's get_window_table / windowed_exp / batch_exp / batch_exp_with_coeff followed by
+ * batch_to_special (depends/libff/libff/algebra/scalar_multiplication/multiexp.tcc:547-583, :585-612, :614-668, :670-720) -- what the
+ * Groth16 generator applies to its A, B, L, H and IC queries (libsnark/zk_proof_systems/ppzksnark/r1cs_gg_ppzksnark/
+ * r1cs_gg_ppzksnark.tcc:293-352).  The table holds, for every window j of w bits, the multiples m 2^(jw) P, m = 1 .. 2^(w-1) (signed
+ * digits: half of libff's 2^w rows per window); one lane walks one scalar through it (csrc/batch_exp_kernels.hip.h, DESIGN.md
+ * section 4.9). */
+typedef struct mnt753_fixed_base mnt753_fixed_base;
+/* get_window_table (multiexp.tcc:547-583) for ONE base point, on the calling thread's current device, with the workspace of one
+ * pass.  point: host pointer, affine wire format (y == 0: the identity -- no table is built, every output is the identity).
+ * window_bits: 0 = chosen by the library (the widest table within the 256 MiB Infinity Cache), else 2 .. 22.
+ * tile: scalars per pass, 0 = automatic (2^17); rounded up to a multiple of the inversion batch, at most 2^24.
+ * The width and the tile belong to the object: there is no process-wide setting and no environment variable.
+ * MNT753_EINVAL: bad ids, a null pointer, a width out of range.  MNT753_ENOMEM: the table (or the workspace) does not fit. */
+int mnt753_fixed_base_create(int curve, int group, const uint64_t* point, int window_bits, size_t tile, mnt753_fixed_base** out);
+int mnt753_fixed_base_free(mnt753_fixed_base* fb);
+/* [0] window bits w, [1] windows W = ceil(754 / w), [2] results per field inversion B, [3] scalars per pass T */
+int mnt753_fixed_base_plan(const mnt753_fixed_base* fb, int out[4]);
+size_t mnt753_fixed_base_table_bytes(const mnt753_fixed_base* fb);
+/* batch_exp / batch_exp_with_coeff followed by batch_to_special (multiexp.tcc:614-720):
+ *   out_affine[i] = (coeff * scalars[i]) * P,  i < n,  affine wire format, identity = all words zero
+ * -- word for word what mnt753_point_to_affine(mnt753_point_scale(..)) gives, so a device output can go straight into
+ * mnt753_bases_create(.., on_device = 1, ..).  scalars: n canonical Fr elements in wire form, only read (the product with the
+ * coefficient goes into the object's workspace).  host_coeff: one Fr element in HOST memory, or NULL for 1.  out_affine must not
+ * overlap scalars.  n = 0 succeeds and writes nothing.  The workspace is sized by T, not by n: longer inputs run in passes, and no
+ * call allocates.  Streams as for mnt753_fft: with both ends on the device the call only enqueues on `stream`; with an end in host
+ * memory it returns when that end is done.  One call in flight per object. */
+int mnt753_batch_exp(mnt753_fixed_base* fb, const uint64_t* scalars, int scalars_on_device, size_t n, const uint64_t* host_coeff,
+                     uint64_t* out_affine, int out_on_device, void* stream);
+/* milliseconds from HIP events: [0] the table build of mnt753_fixed_base_create, [1] the walk and [2] the normalisation of the LAST
+ * pass of the last mnt753_batch_exp call (the whole call when n <= T); waits for that pass.  Zeros before the first call. */
+int mnt753_fixed_base_last_timing(mnt753_fixed_base* fb, float out_ms[3]);
+
 /* ---- FFT over Fr ---------------------------------------------------------------------------------- */
 typedef struct mnt753_domain mnt753_domain;
 /* libfqfft's basic_radix2_domain of exactly m elements: the constructor accepts every power of two m <= 2^s (s = 30 MNT4753,

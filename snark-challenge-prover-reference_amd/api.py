@@ -112,6 +112,12 @@ def lib():
         "mnt753_check_scalars": (i, [i, vp, i, sz, C.POINTER(CheckReport), vp]),
         "mnt753_check_products": (i, [i, vp, vp, vp, sz, C.POINTER(CheckReport), vp]),
         "mnt753_r1cs_check": (i, [vp, vp, C.POINTER(CheckReport), vp]),
+        "mnt753_fixed_base_create": (i, [i, i, vp, i, sz, C.POINTER(vp)]),
+        "mnt753_fixed_base_free": (i, [vp]),
+        "mnt753_fixed_base_plan": (i, [vp, C.POINTER(C.c_int)]),
+        "mnt753_fixed_base_table_bytes": (sz, [vp]),
+        "mnt753_fixed_base_last_timing": (i, [vp, C.POINTER(C.c_float)]),
+        "mnt753_batch_exp": (i, [vp, vp, i, sz, vp, vp, i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)   # AttributeError here = the library does not export what the header declares
@@ -496,6 +502,63 @@ def check_products(curve, dev_a, dev_b, dev_c, n, stream=None):
     _check(lib().mnt753_check_products(curve, C.c_void_p(int(dev_a)), C.c_void_p(int(dev_b)), C.c_void_p(int(dev_c)), int(n), C.byref(rep), st),
            "mnt753_check_products")
     return _report(rep)
+
+
+class FixedBase:
+    """One base point with its window table on the device (mnt753_fixed_base_*): libff's get_window_table, and batch_exp /
+    batch_exp_with_coeff + batch_to_special as `batch_exp`.  window_bits = 0 and tile = 0 leave the width and the scalars per pass to
+    the library; both belong to the object."""
+
+    def __init__(self, curve, group, point, window_bits=0, tile=0):
+        self.curve, self.group = curve, group
+        self._h = C.c_void_p()
+        p = np.ascontiguousarray(point, dtype=np.uint64)
+        assert p.size == affine_words(curve, group)
+        _check(lib().mnt753_fixed_base_create(curve, group, C.c_void_p(p.ctypes.data), int(window_bits), int(tile), C.byref(self._h)),
+               "mnt753_fixed_base_create")
+
+    def plan(self):
+        t = (C.c_int * 4)()
+        _check(lib().mnt753_fixed_base_plan(self._h, t), "mnt753_fixed_base_plan")
+        return dict(window_bits=t[0], windows=t[1], inversion_batch=t[2], tile=t[3])
+
+    @property
+    def table_bytes(self):
+        return int(lib().mnt753_fixed_base_table_bytes(self._h))
+
+    def last_timing(self):
+        """HIP-event milliseconds: the table build, and the walk and the normalisation of the last pass of the last batch_exp"""
+        t = (C.c_float * 3)()
+        _check(lib().mnt753_fixed_base_last_timing(self._h, t), "mnt753_fixed_base_last_timing")
+        return dict(table_build_ms=t[0], walk_ms=t[1], normalise_ms=t[2])
+
+    def batch_exp(self, scalars, coeff=None, on_device=False, out_ptr=None, stream=None, n=None):
+        """out[i] = (coeff * scalars[i]) * P in affine wire form.  scalars: a numpy array [n, 12], or with on_device a device address
+        and n.  Without out_ptr the result comes back as a numpy array [n, affine_words]; with out_ptr (a device address with room for
+        n points) it stays on the device and the call returns None."""
+        sptr, cnt, keep = _input_ptr(scalars, on_device, 12, n)
+        kc = None if coeff is None else np.ascontiguousarray(coeff, dtype=np.uint64)
+        assert kc is None or kc.size == 12
+        cptr = C.c_void_p(kc.ctypes.data) if kc is not None else C.c_void_p()
+        st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+        if out_ptr is None:
+            out = np.zeros((cnt, affine_words(self.curve, self.group)), dtype=np.uint64)
+            optr, out_dev = C.c_void_p(out.ctypes.data if cnt else 0), 0
+        else:
+            out, optr, out_dev = None, C.c_void_p(int(out_ptr)), 1
+        _check(lib().mnt753_batch_exp(self._h, sptr, 1 if on_device else 0, cnt, cptr, optr, out_dev, st), "mnt753_batch_exp")
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().mnt753_fixed_base_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def read_r1cs_file(path):
