@@ -299,6 +299,22 @@ int mnt753_compute_h(mnt753_domain* d, uint64_t* dev_ca, uint64_t* dev_cb, uint6
 int mnt753_compute_h_chain(mnt753_domain* d, uint64_t* dev_vec, void* stream);
 int mnt753_compute_h_finish(mnt753_domain* d, uint64_t* dev_a, const uint64_t* dev_b, const uint64_t* dev_c, uint64_t* dev_h, void* stream);
 int mnt753_domain_device(const mnt753_domain* d);   /* logical device the domain lives on */
+/* ---- the domain at a point: what a Groth16 generator needs of it ------------------------------------
+ * t: one canonical Fr element in HOST memory, wire form; t >= r is MNT753_EINVAL and nothing is enqueued.  All kinds of domain.
+ * replaces evaluation_domain::compute_vanishing_polynomial(t) (t^m - 1 for basic and mixed domains; extended_radix2_domain.tcc:155-158,
+ * step_radix2_domain.tcc:230-233): host arithmetic, a handful of products; host_zt receives one element. */
+int mnt753_domain_vanishing_at(mnt753_domain* d, const uint64_t* host_t, uint64_t* host_zt);
+/* replaces evaluation_domain::evaluate_all_lagrange_polynomials(t) (basic_radix2_domain_aux.tcc:333-395 for basic and mixed domains,
+ * extended_radix2_domain.tcc:120-139, step_radix2_domain.tcc:189-214): dev_u receives the m = mnt753_domain_size(d) values L_i(t), the
+ * same words the reference computes, also where t is an element of the domain (the indicator vector of its index, as the reference
+ * returns it) and for t = 0.  The m inversions of the reference are one inversion per 16 elements on the device (csrc/qap_kernels.hip.h);
+ * the few scalars of a call are computed on the host.  The first call allocates a workspace of 112 bytes per element that stays with
+ * the domain; later calls only enqueue on `stream`.  The workspace is shared like the work buffer of mnt753_fft: calls on one domain
+ * (this one and the transforms) on different streams are ordered on the device, and host threads must not enter the same domain at
+ * the same time -- calls on one domain are not concurrent. */
+int mnt753_domain_lagrange_at(mnt753_domain* d, const uint64_t* host_t, uint64_t* dev_u /* d->m elements */, void* stream);
+/* dev_out[i] = t^i, i < n: the Ht of r1cs_to_qap.tcc:155-159.  n = 0 succeeds and writes nothing. */
+int mnt753_vec_powers(int curve, const uint64_t* host_t, uint64_t* dev_out, size_t n, void* stream);   /* 1, t, ..., t^(n-1) */
 
 /* ---- witness-map front end (the step before the hot path) -------------------------------------------
  * The reference evaluates the constraint system on the assignment on the CPU before the prover starts
@@ -317,6 +333,34 @@ size_t mnt753_r1cs_domain_size(const mnt753_r1cs* r);   /* nc + num_inputs + 1 *
 size_t mnt753_r1cs_num_variables(const mnt753_r1cs* r); /* m: dev_w of mnt753_r1cs_evaluate must hold m + 1 elements */
 size_t mnt753_r1cs_num_inputs(const mnt753_r1cs* r);
 int mnt753_r1cs_evaluate(mnt753_r1cs* r, const uint64_t* dev_w, uint64_t* dev_ca, uint64_t* dev_cb, uint64_t* dev_cc, size_t out_len, void* stream);
+/* The instance map with evaluation: replaces r1cs_to_qap_instance_map_with_evaluation (libsnark/reductions/r1cs_to_qap/r1cs_to_qap.tcc:
+ * 105-175), the call every libsnark generator starts with (r1cs_gg_ppzksnark.tcc:223).  With u = the Lagrange coefficients of d at t:
+ *   At[i] = u[nc + i] for i <= num_inputs;  every term (row, col, coeff) of a / b / c adds u[row] coeff to At / Bt / Ct[col];
+ *   Ht[i] = t^i for i <= m_d = mnt753_domain_size(d);  Zt = Z(t).
+ * dev_At / dev_Bt / dev_Ct: num_variables + 1 elements each, dev_Ht: m_d + 1, host_Zt: one element in host memory (written before the
+ * call returns; the device vectors are complete when `stream` has run).  MNT753_EINVAL, with nothing enqueued and nothing written: a
+ * null pointer, a domain of the other curve or on another device, m_d < nc + num_inputs + 1, t >= r.
+ * The sums go by column and the matrices lie by row: the first call on a system builds a column-major view of it (a permutation of
+ * 8 bytes per term, on the host, from the index arrays copied back from the device) and keeps it until mnt753_r1cs_free;
+ * mnt753_r1cs_create and the prover path pay nothing for it.  Every column is cut into chunks of at most chunk_terms terms, one device
+ * thread each, so that a column holding a large share of all terms (the constant, column 0) does not serialise behind one lane.
+ * The partial sums and the copy of u belong to the system and are shared by its calls: calls on different streams are ordered on the
+ * device one after the other (an event per system, as for a domain's work buffer), and host threads must not enter the same system
+ * at the same time.  The system lives on the device that was current when it was created and the call runs there; a domain on
+ * another device is MNT753_EINVAL. */
+typedef struct {
+  uint32_t chunk_terms, reserved;   /* L: terms per chunk at most */
+  uint64_t terms;                   /* terms of a, b and c together */
+  uint64_t work_items;              /* chunks = threads of the column-sum kernel */
+  uint64_t split_columns;           /* columns cut into more than one chunk */
+  uint64_t longest_column;          /* terms of the longest column */
+  uint64_t transpose_bytes;         /* device memory of the column-major view (permutation, chunk and work lists) */
+  uint64_t partial_bytes;           /* device memory of the partial sums, 112 bytes per chunk */
+} mnt753_qap_plan;
+/* the plan of a system; builds the column-major view if no call has yet */
+int mnt753_r1cs_qap_plan(const mnt753_r1cs* r, mnt753_qap_plan* out);
+int mnt753_r1cs_qap_at(mnt753_r1cs* r, mnt753_domain* d, const uint64_t* host_t, uint64_t* dev_At, uint64_t* dev_Bt, uint64_t* dev_Ct,
+                       uint64_t* dev_Ht, uint64_t* host_Zt, void* stream);
 
 /* ---- input validation (device) --------------------------------------------------------------------------
  * The reference prover trusts its files (unchecked fread, prover_reference_functions.cpp:48-116); what the reference HAS for the

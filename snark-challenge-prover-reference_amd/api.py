@@ -20,6 +20,12 @@ class Mnt753Error(RuntimeError):
 BAD_NONE, BAD_NONCANONICAL, BAD_OFF_CURVE, BAD_UNSATISFIED = 0, 1, 2, 3
 
 
+class QapPlan(C.Structure):
+    """mnt753_qap_plan"""
+    _fields_ = [("chunk_terms", C.c_uint32), ("reserved", C.c_uint32), ("terms", C.c_uint64), ("work_items", C.c_uint64),
+                ("split_columns", C.c_uint64), ("longest_column", C.c_uint64), ("transpose_bytes", C.c_uint64), ("partial_bytes", C.c_uint64)]
+
+
 class CheckReport(C.Structure):
     """mnt753_check_report"""
     _fields_ = [("n_bad", C.c_uint64), ("first_bad", C.c_uint64), ("first_reason", C.c_uint32), ("reserved", C.c_uint32)]
@@ -101,6 +107,11 @@ def lib():
         "mnt753_compute_h_chain": (i, [vp, vp, vp]),
         "mnt753_compute_h_finish": (i, [vp, vp, vp, vp, vp, vp]),
         "mnt753_domain_device": (i, [vp]),
+        "mnt753_domain_vanishing_at": (i, [vp, u64p, u64p]),
+        "mnt753_domain_lagrange_at": (i, [vp, u64p, vp, vp]),
+        "mnt753_vec_powers": (i, [i, u64p, vp, sz, vp]),
+        "mnt753_r1cs_qap_plan": (i, [vp, C.POINTER(QapPlan)]),
+        "mnt753_r1cs_qap_at": (i, [vp, vp, u64p, vp, vp, vp, vp, u64p, vp]),
         "mnt753_synth_scalars": (i, [i, C.c_uint64, sz, u64p]),
         "mnt753_r1cs_create": (i, [i, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
         "mnt753_r1cs_free": (i, [vp]),
@@ -402,6 +413,29 @@ class Domain:
         _check(lib().mnt753_compute_h_finish(self._h, C.c_void_p(int(a)), C.c_void_p(int(b)), C.c_void_p(int(c)), C.c_void_p(int(h)), st),
                "mnt753_compute_h_finish")
 
+    def vanishing_at(self, t):
+        """Z(t) of the domain (compute_vanishing_polynomial): t and the result are 12 uint64 in wire form, on the host."""
+        k, pk = _fr_elem(t)
+        out = np.zeros(12, dtype=np.uint64)
+        _check(lib().mnt753_domain_vanishing_at(self._h, pk, out.ctypes.data_as(C.POINTER(C.c_uint64))), "mnt753_domain_vanishing_at")
+        return out
+
+    def lagrange_at(self, t, out_ptr=None, stream=None):
+        """The m Lagrange coefficients L_i(t) of the domain (evaluate_all_lagrange_polynomials).  Without out_ptr they come back as a
+        numpy array [m, 12]; with out_ptr (a device address with room for m elements) they stay on the device and the call returns None."""
+        k, pk = _fr_elem(t)
+        st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+        if out_ptr is not None:
+            _check(lib().mnt753_domain_lagrange_at(self._h, pk, C.c_void_p(int(out_ptr)), st), "mnt753_domain_lagrange_at")
+            return None
+        buf = DeviceBuffer(96 * self.m)
+        try:
+            _check(lib().mnt753_domain_lagrange_at(self._h, pk, buf.ptr, st), "mnt753_domain_lagrange_at")
+            _check(lib().mnt753_sync(st), "mnt753_sync")
+            return buf.to_numpy().reshape(self.m, 12)
+        finally:
+            buf.close()
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib().mnt753_domain_free(self._h)
@@ -412,6 +446,29 @@ class Domain:
             self.close()
         except Exception:
             pass
+
+
+def _fr_elem(t):
+    """one Fr element in wire form -> (array to keep alive, uint64 pointer)"""
+    k = np.ascontiguousarray(t, dtype=np.uint64).reshape(-1)
+    assert k.size == 12
+    return k, k.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def vec_powers(curve, t, n, out_ptr=None, stream=None):
+    """1, t, .., t^(n-1) in Fr of the curve (mnt753_vec_powers); a numpy array [n, 12], or None with out_ptr (a device address)."""
+    k, pk = _fr_elem(t)
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    if out_ptr is not None:
+        _check(lib().mnt753_vec_powers(curve, pk, C.c_void_p(int(out_ptr)), int(n), st), "mnt753_vec_powers")
+        return None
+    buf = DeviceBuffer(96 * max(int(n), 1))
+    try:
+        _check(lib().mnt753_vec_powers(curve, pk, buf.ptr, int(n), st), "mnt753_vec_powers")
+        _check(lib().mnt753_sync(st), "mnt753_sync")
+        return buf.to_numpy().reshape(-1, 12)[:int(n)]
+    finally:
+        buf.close()
 
 
 def vec_muleq(curve, a_ptr, b_ptr, n, stream=None):
@@ -604,6 +661,30 @@ class R1cs:
         st = C.c_void_p(int(stream)) if stream else C.c_void_p()
         _check(lib().mnt753_r1cs_check(self._h, C.c_void_p(int(dev_w)), C.byref(rep), st), "mnt753_r1cs_check")
         return _report(rep)
+
+    def qap_plan(self):
+        """mnt753_r1cs_qap_plan: how qap_at cuts the columns (builds the column-major view if no call has yet)."""
+        p = QapPlan()
+        _check(lib().mnt753_r1cs_qap_plan(self._h, C.byref(p)), "mnt753_r1cs_qap_plan")
+        return dict(chunk_terms=int(p.chunk_terms), terms=int(p.terms), work_items=int(p.work_items), split_columns=int(p.split_columns),
+                    longest_column=int(p.longest_column), transpose_bytes=int(p.transpose_bytes), partial_bytes=int(p.partial_bytes))
+
+    def qap_at(self, domain, t, out=None, stream=None):
+        """r1cs_to_qap_instance_map_with_evaluation at t on `domain` (mnt753_r1cs_qap_at).  out: device addresses (At, Bt, Ct, Ht) with
+        room for m + 1, m + 1, m + 1 and domain.m + 1 elements, or None for four new DeviceBuffers.  Returns (At, Bt, Ct, Ht, Zt): the
+        four device buffers (or the addresses given) and Zt as 12 uint64 on the host; the vectors are complete when `stream` has run."""
+        k, pk = _fr_elem(t)
+        st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+        if out is None:
+            bufs = [DeviceBuffer(96 * (self.m + 1)) for _ in range(3)] + [DeviceBuffer(96 * (domain.m + 1))]
+            ptrs = [b.ptr for b in bufs]
+        else:
+            bufs = list(out)
+            ptrs = [C.c_void_p(int(p)) for p in out]
+        zt = np.zeros(12, dtype=np.uint64)
+        _check(lib().mnt753_r1cs_qap_at(self._h, domain._h, pk, ptrs[0], ptrs[1], ptrs[2], ptrs[3], zt.ctypes.data_as(C.POINTER(C.c_uint64)), st),
+               "mnt753_r1cs_qap_at")
+        return bufs[0], bufs[1], bufs[2], bufs[3], zt
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

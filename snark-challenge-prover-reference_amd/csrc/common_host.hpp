@@ -11,6 +11,8 @@ int set_hip_error(hipError_t e, const char* what, const char* file, int line);
 int require_device();
 // physical HIP ordinal of the calling thread's current logical device (mnt753_set_device), -1 before initialisation
 int current_physical_device();
+// the curve of an evaluation domain (csrc/mnt753_fft.hip), -1 for a null domain: for entry points outside that file
+int domain_curve(const mnt753_domain* d);
 // Every entry point that takes an object living on one device (a base set, an evaluation domain) runs on that device and puts the
 // thread back on its own afterwards.  HIP's own notion of the thread's current device, not the library's bookkeeping: a host thread
 // that never called mnt753_set_device, or whose device PyTorch changed, still gets its kernels, events and allocations on the object's GPU.

@@ -10,6 +10,7 @@
 #include "common_host.hpp"
 #include "host_field.hpp"
 #include "ntt_kernels.hip.h"
+#include "qap_kernels.hip.h"
 
 using namespace mnt753;
 using namespace mnt753::host;
@@ -45,6 +46,7 @@ struct mnt753_domain {
   // (e < 5 each), consts as in a basic domain (Z is one constant).  The step / extended fields above stay unused.
   unsigned q_n = 0, q_pow = 0;
   size_t t_n = 0;
+  uint32_t *lag_pre = nullptr;                         // mnt753_domain_lagrange_at: the prefix products of its inversion runs (m entries), allocated by the first call
 };
 
 namespace {
@@ -585,7 +587,85 @@ Pick select_domain(int frm, size_t min_size, unsigned flags) {
   return refuse(name, min_size, "a geometric or arithmetic sequence domain of size %zu (past candidate 7)", min_size);
 }
 
+// ---- the Lagrange coefficients and Z at a point ----------------------------------------------------------
+// The handful of scalars of a call (t^n, Z, 1 / n, the coefficients of the two halves of an extended or step domain) are computed
+// here, on the host, and travel as kernel arguments; the work per element is qap_kernels.hip.h.
+template <int M>
+WireElem wire_of(const HFp<M>& v) { WireElem w; memcpy(w.w, v.l, 96); return w; }
+template <int M>
+HFp<M> step_omega(const mnt753_domain* d) {          // the root of order 2 big_m of a step domain (step_radix2_domain.tcc:21-53)
+  HFp<M> omega = HFp<M>::from_words(FRD[M].root_of_unity);
+  for (int i = FRD[M].two_adicity; i > ceil_log2(d->m); --i) omega = omega.squared();
+  return omega;
+}
+template <int M>
+HFp<M> vanishing_t(const mnt753_domain* d, const HFp<M>& t) {
+  typedef HFp<M> Fr;
+  const Fr one = Fr::one();
+  if (d->kind == MNT753_DOMAIN_EXTENDED) {           // extended_radix2_domain.tcc:155-158
+    const Fr g = Fr::from_words(FRD[M].mult_gen), ts = t.pow_u64((uint64_t)d->small_m);
+    return (ts - one) * (ts - g.squared().pow_u64((uint64_t)d->small_m));
+  }
+  if (d->kind == MNT753_DOMAIN_STEP)                 // step_radix2_domain.tcc:230-233
+    return (t.pow_u64((uint64_t)d->big_m) - one) * (t.pow_u64((uint64_t)d->small_m) - step_omega<M>(d).pow_u64((uint64_t)d->small_m));
+  return t.pow_u64((uint64_t)d->m) - one;            // basic and mixed: t^m - 1
+}
+// _basic_radix2_evaluate_all_lagrange_polynomials(n, t) times `coeff` into elements [off, off + n) of out
+// (basic_radix2_domain_aux.tcc:333-395).  tab: omega^j of the subgroup (half: j < n / 2 only), null for n == 1.  os != null: the big
+// half of a step domain, whose element i is also divided by omega_big^(i stride) - *os.
+template <int M>
+int lagrange_sub(mnt753_domain* d, const uint32_t* tab, size_t n, bool half, uint32_t* out, size_t off, const HFp<M>& t, const HFp<M>& coeff,
+                 const HFp<M>* os, size_t stride, hipStream_t st) {
+  typedef HFp<M> Fr;
+  const Fr one = Fr::one();
+  const Fr tn = t.pow_u64((uint64_t)n);
+  if (n == 1 || tn == one) {
+    // t is an element of the subgroup: Z = 0 and nothing may be inverted.  The indicator vector, times the factors the outer formulas
+    // put on the matching element (omega_big^(i stride) = t^stride there).
+    Fr value = coeff;
+    if (os) value = value * (t.pow_u64((uint64_t)stride) - *os).inverse();
+    hipLaunchKernelGGL((k_lagrange_indicator<M>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n == 1 ? nullptr : tab, n, half ? 1 : 0,
+                       out + off * 24, wire_of(t), wire_of(value));
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
+  const Fr c = (tn - one) * Fr::from_uint((uint64_t)n).inverse() * coeff;
+  const size_t runs = (n + LAG_INV_BATCH - 1) / LAG_INV_BATCH;
+  const unsigned g = (unsigned)((runs + 255) / 256);
+  uint32_t* pre = d->lag_pre + off * FPS_WORDS;
+  if (os) hipLaunchKernelGGL((k_lagrange_run<M, true>), dim3(g), dim3(256), 0, st, tab, n, half ? 1 : 0, pre, out + off * 24, wire_of(t), wire_of(c), wire_of(*os), stride);
+  else hipLaunchKernelGGL((k_lagrange_run<M, false>), dim3(g), dim3(256), 0, st, tab, n, half ? 1 : 0, pre, out + off * 24, wire_of(t), wire_of(c), wire_of(one), (size_t)0);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+template <int M>
+int lagrange_t(mnt753_domain* d, const uint64_t* host_t, uint32_t* out, hipStream_t st) {
+  typedef HFp<M> Fr;
+  const Fr one = Fr::one(), t = Fr::from_words(host_t);
+  if (d->kind == MNT753_DOMAIN_BASIC) return lagrange_sub<M>(d, d->tw_fwd, d->m, true, out, 0, t, one, nullptr, 0, st);
+  if (d->kind == MNT753_DOMAIN_MIXED) return lagrange_sub<M>(d, d->x_fwd, d->m, false, out, 0, t, one, nullptr, 0, st);
+  const size_t big_m = d->big_m, small_m = d->small_m;
+  if (d->kind == MNT753_DOMAIN_EXTENDED) {           // extended_radix2_domain.tcc:120-139
+    const Fr shift = Fr::from_words(FRD[M].mult_gen).squared();
+    const Fr ts = t.pow_u64((uint64_t)small_m), ss = shift.pow_u64((uint64_t)small_m);
+    const Fr one_over_denom = (ss - one).inverse();
+    const Fr t0_coeff = (ts - ss) * (-one_over_denom), t1_coeff = (ts - one) * one_over_denom;
+    if (int rc = lagrange_sub<M>(d, d->sub_big->tw_fwd, small_m, true, out, 0, t, t0_coeff, nullptr, 0, st)) return rc;
+    return lagrange_sub<M>(d, d->sub_big->tw_fwd, small_m, true, out, small_m, t * shift.inverse(), t1_coeff, nullptr, 0, st);
+  }
+  // step_radix2_domain.tcc:189-214
+  const Fr omega = step_omega<M>(d), os = omega.pow_u64((uint64_t)small_m);
+  const Fr l0 = t.pow_u64((uint64_t)small_m) - os;
+  const Fr l1 = (t.pow_u64((uint64_t)big_m) - one) * (omega.pow_u64((uint64_t)big_m) - one).inverse();
+  if (int rc = lagrange_sub<M>(d, d->sub_big->tw_fwd, big_m, true, out, 0, t, l0, &os, small_m, st)) return rc;
+  return lagrange_sub<M>(d, d->sub_small ? d->sub_small->tw_fwd : nullptr, small_m, true, out, big_m, t * omega.inverse(), l1, nullptr, 0, st);
+}
+
 }  // namespace
+
+namespace mnt753 {
+int domain_curve(const mnt753_domain* d) { return d ? d->curve : -1; }
+}
 
 extern "C" {
 
@@ -636,7 +716,7 @@ int mnt753_domain_free(mnt753_domain* d) {
   if (d->sub_big) mnt753_domain_free(d->sub_big);
   OnDevice on(d->device);
   void* ptrs[] = {d->tw_fwd, d->tw_inv, d->cos_fwd, d->cos_fwd_s, d->cos_inv_s, d->consts, d->work, d->stage,
-                  d->x_fwd, d->x_inv, d->x_inv2, d->xcos_fwd, d->xcos_inv, d->xconsts, d->zt, d->zt12};
+                  d->x_fwd, d->x_inv, d->x_inv2, d->xcos_fwd, d->xcos_inv, d->xconsts, d->zt, d->zt12, d->lag_pre};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (d->work_free) (void)hipEventDestroy(d->work_free);
   delete d;
@@ -757,6 +837,50 @@ int mnt753_compute_h_finish(mnt753_domain* d, uint64_t* dev_a, const uint64_t* d
   uint32_t* h = reinterpret_cast<uint32_t*>(dev_h);
   const int rc = d->frm == MOD_A ? h_finish_t<MOD_A>(d, a, b, c, h, (hipStream_t)stream) : h_finish_t<MOD_B>(d, a, b, c, h, (hipStream_t)stream);
   return work_release(d, (hipStream_t)stream, rc);
+}
+
+static bool fr_canonical(int frm, const uint64_t* w) { return frm == MOD_A ? !HFp<MOD_A>::geq_p(w) : !HFp<MOD_B>::geq_p(w); }
+
+int mnt753_domain_vanishing_at(mnt753_domain* d, const uint64_t* host_t, uint64_t* host_zt) {
+  if (!d || !host_t || !host_zt) return set_error(MNT753_EINVAL, "domain_vanishing_at: null argument");
+  if (!fr_canonical(d->frm, host_t)) return set_error(MNT753_EINVAL, "domain_vanishing_at: t is not a canonical element of Fr");
+  if (d->frm == MOD_A) memcpy(host_zt, vanishing_t<MOD_A>(d, HFp<MOD_A>::from_words(host_t)).l, 96);
+  else memcpy(host_zt, vanishing_t<MOD_B>(d, HFp<MOD_B>::from_words(host_t)).l, 96);
+  return 0;
+}
+
+int mnt753_domain_lagrange_at(mnt753_domain* d, const uint64_t* host_t, uint64_t* dev_u, void* stream) {
+  if (!d || !host_t || !dev_u) return set_error(MNT753_EINVAL, "domain_lagrange_at: null argument");
+  if (!fr_canonical(d->frm, host_t)) return set_error(MNT753_EINVAL, "domain_lagrange_at: t is not a canonical element of Fr");
+  if (int rc = require_device()) return rc;
+  OnDevice on(d->device);
+  if (!d->lag_pre) {
+    if (hipMalloc(&d->lag_pre, d->m * FPS_WORDS * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      d->lag_pre = nullptr;
+      return set_error(MNT753_ENOMEM, "domain_lagrange_at: device allocation failed");
+    }
+  }
+  if (int rc = work_acquire(d, (hipStream_t)stream)) return rc;      // lag_pre is shared like `work`: calls on different streams are ordered
+  uint32_t* u = reinterpret_cast<uint32_t*>(dev_u);
+  const int rc = d->frm == MOD_A ? lagrange_t<MOD_A>(d, host_t, u, (hipStream_t)stream) : lagrange_t<MOD_B>(d, host_t, u, (hipStream_t)stream);
+  return work_release(d, (hipStream_t)stream, rc);
+}
+
+int mnt753_vec_powers(int curve, const uint64_t* host_t, uint64_t* dev_out, size_t n, void* stream) {
+  if (curve < 0 || curve > 1 || !host_t || (n && !dev_out)) return set_error(MNT753_EINVAL, "vec_powers: bad argument");
+  if (!fr_canonical(curve == MNT753_CURVE_MNT4753 ? MOD_A : MOD_B, host_t)) return set_error(MNT753_EINVAL, "vec_powers: t is not a canonical element of Fr");
+  if (int rc = require_device()) return rc;
+  if (n == 0) return 0;
+  WireElem t;
+  memcpy(t.w, host_t, 96);
+  const size_t runs = (n + POW_RUN - 1) / POW_RUN;
+  const unsigned g = (unsigned)((runs + 255) / 256);
+  uint32_t* out = reinterpret_cast<uint32_t*>(dev_out);
+  if (curve == MNT753_CURVE_MNT4753) hipLaunchKernelGGL((k_vec_powers<MOD_A>), dim3(g), dim3(256), 0, (hipStream_t)stream, out, t, n);
+  else hipLaunchKernelGGL((k_vec_powers<MOD_B>), dim3(g), dim3(256), 0, (hipStream_t)stream, out, t, n);
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 
 }  // extern "C"

@@ -16,11 +16,16 @@
 // 2^20-row system and reports the achieved GB/s.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstring>
+#include <mutex>
 #include <new>
 #include <vector>
 
 #include "common_host.hpp"
+#include "host_field.hpp"
 #include "msm_kernels.hip.h"
+#include "qap_kernels.hip.h"
+#include "qap_transpose.hpp"
 
 using namespace mnt753;
 
@@ -32,6 +37,19 @@ struct mnt753_r1cs {
   uint32_t* coeff[3] = {nullptr, nullptr, nullptr};     // device radix, FPS_WORDS per term
   uint64_t nnz[3] = {0, 0, 0};
   uint64_t* work = nullptr;                             // device, 3 nc items (which * nc + row), longest rows first
+  int device = 0, logical_device = 0;                   // physical HIP ordinal / logical device the system lives on (the creating thread's current device)
+  // the column-major view of mnt753_r1cs_qap_at (qap_transpose.hpp): built by the first call that needs it, never by the prover path.
+  // mutable: the view is a cache of the (const) system, which mnt753_r1cs_qap_plan may have to fill
+  mutable std::mutex qap_mutex;
+  mutable bool qap_built = false;
+  mutable mnt753_qap_plan qap_plan = {};
+  mutable uint32_t *qap_perm_row = nullptr, *qap_perm_k = nullptr, *qap_chunk_len = nullptr, *qap_order = nullptr;   // device
+  mutable uint64_t *qap_chunk_start = nullptr, *qap_col_chunk = nullptr;                                            // device
+  mutable uint32_t* qap_partial = nullptr;              // device, one partial sum (FPS_WORDS) per chunk
+  mutable uint64_t qap_base[4] = {0, 0, 0, 0};
+  uint32_t* qap_u = nullptr;                            // device, the Lagrange coefficients of the last call's domain (wire form)
+  size_t qap_u_cap = 0;
+  hipEvent_t qap_free = nullptr;                        // recorded behind every qap_at: the next one (any stream) waits for it before it touches qap_u / qap_partial
 };
 
 namespace {
@@ -95,6 +113,57 @@ __global__ void __launch_bounds__(256) k_r1cs_evaluate(const uint64_t* __restric
   fp_pack(wv, canon);
   store_wire24(dst, wv);
 }
+// the column-major view, once per system: the row-major index arrays come back from the device (mnt753_r1cs_create keeps no host
+// copy: a prover pays nothing for this), the permutation is built on the host and uploaded
+int qap_prepare(const mnt753_r1cs* r) {
+  OnDevice on(r->device);
+  std::lock_guard<std::mutex> lock(r->qap_mutex);
+  if (r->qap_built) return 0;
+  std::vector<uint64_t> rp[3];
+  std::vector<uint32_t> cl[3];
+  const uint64_t* rpp[3];
+  const uint32_t* clp[3];
+  for (int k = 0; k < 3; ++k) {
+    rp[k].resize(r->nc + 1);
+    cl[k].resize(r->nnz[k] + 1);
+    HIP_TRY(hipMemcpy(rp[k].data(), r->row_ptr[k], 8 * (r->nc + 1), hipMemcpyDeviceToHost));
+    if (r->nnz[k]) HIP_TRY(hipMemcpy(cl[k].data(), r->col[k], 4 * r->nnz[k], hipMemcpyDeviceToHost));
+    rpp[k] = rp[k].data();
+    clp[k] = cl[k].data();
+  }
+  QapTranspose tr;
+  if (!qap_build_transpose(r->nc, r->m + 1, rpp, clp, QAP_CHUNK_TERMS, tr)) return set_error(MNT753_EINVAL, "r1cs_qap_at: the system is too large for 32-bit term indices");
+  const size_t n_chunks = tr.order.size(), total = tr.perm_row.size();
+  auto up = [](auto** dst, const auto& v) -> hipError_t {
+    typedef typename std::remove_reference<decltype(v[0])>::type T;
+    hipError_t e = hipMalloc(dst, sizeof(T) * (v.size() + 1));
+    if (e == hipSuccess && !v.empty()) e = hipMemcpy(*dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
+    return e;
+  };
+  hipError_t e = up(&r->qap_perm_row, tr.perm_row);
+  if (e == hipSuccess) e = up(&r->qap_perm_k, tr.perm_k);
+  if (e == hipSuccess) e = up(&r->qap_chunk_start, tr.chunk_start);
+  if (e == hipSuccess) e = up(&r->qap_chunk_len, tr.chunk_len);
+  if (e == hipSuccess) e = up(&r->qap_col_chunk, tr.col_chunk);
+  if (e == hipSuccess) e = up(&r->qap_order, tr.order);
+  if (e == hipSuccess) e = hipMalloc(&r->qap_partial, 4 * FPS_WORDS * (n_chunks + 1));
+  if (e != hipSuccess) {
+    void** qap[] = {(void**)&r->qap_perm_row, (void**)&r->qap_perm_k, (void**)&r->qap_chunk_len, (void**)&r->qap_order, (void**)&r->qap_chunk_start,
+                    (void**)&r->qap_col_chunk, (void**)&r->qap_partial};
+    for (void** p : qap) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    return set_hip_error(e, "r1cs_qap_at: column-major view", __FILE__, __LINE__);
+  }
+  for (int k = 0; k < 4; ++k) r->qap_base[k] = tr.base[k];
+  r->qap_plan.chunk_terms = tr.L;
+  r->qap_plan.terms = total;
+  r->qap_plan.work_items = n_chunks;
+  r->qap_plan.split_columns = tr.split_columns;
+  r->qap_plan.longest_column = tr.longest_column;
+  r->qap_plan.transpose_bytes = tr.device_bytes();
+  r->qap_plan.partial_bytes = 4 * FPS_WORDS * n_chunks;
+  r->qap_built = true;
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -117,6 +186,7 @@ int mnt753_r1cs_create(int curve, uint64_t num_inputs, uint64_t m, uint64_t nc, 
   if (!r) return set_error(MNT753_ENOMEM, "r1cs_create: host allocation failed");
   r->curve = curve; r->frm = curve == MNT753_CURVE_MNT4753 ? MOD_A : MOD_B;
   r->num_inputs = num_inputs; r->m = m; r->nc = nc;
+  r->device = current_physical_device(); r->logical_device = mnt753_get_device();
   for (int k = 0; k < 3; ++k) {
     const uint64_t nnz = row_ptr[k][nc];
     r->nnz[k] = nnz;
@@ -169,6 +239,9 @@ int mnt753_r1cs_create(int curve, uint64_t num_inputs, uint64_t m, uint64_t nc, 
 int mnt753_r1cs_free(mnt753_r1cs* r) {
   if (!r) return 0;
   if (r->work) (void)hipFree(r->work);
+  void* qap[] = {r->qap_perm_row, r->qap_perm_k, r->qap_chunk_len, r->qap_order, r->qap_chunk_start, r->qap_col_chunk, r->qap_partial, r->qap_u};
+  for (void* p : qap) if (p) (void)hipFree(p);
+  if (r->qap_free) (void)hipEventDestroy(r->qap_free);
   for (int k = 0; k < 3; ++k) {
     if (r->row_ptr[k]) (void)hipFree(r->row_ptr[k]);
     if (r->col[k]) (void)hipFree(r->col[k]);
@@ -211,6 +284,57 @@ int mnt753_r1cs_check(mnt753_r1cs* r, const uint64_t* dev_w, mnt753_check_report
   if (rc == 0) rc = mnt753_check_products(r->curve, scratch, scratch + 12 * n, scratch + 24 * n, n, out, stream);
   (void)hipFree(scratch);
   return rc;
+}
+
+int mnt753_r1cs_qap_plan(const mnt753_r1cs* r, mnt753_qap_plan* out) {
+  if (!r || !out) return set_error(MNT753_EINVAL, "r1cs_qap_plan: null argument");
+  if (int rc = require_device()) return rc;
+  if (int rc = qap_prepare(r)) return rc;
+  *out = r->qap_plan;
+  return 0;
+}
+
+// r1cs_to_qap_instance_map_with_evaluation (r1cs_to_qap.tcc:110-159) on the device
+int mnt753_r1cs_qap_at(mnt753_r1cs* r, mnt753_domain* d, const uint64_t* host_t, uint64_t* dev_At, uint64_t* dev_Bt, uint64_t* dev_Ct, uint64_t* dev_Ht,
+                       uint64_t* host_Zt, void* stream) {
+  if (!r || !d || !host_t || !dev_At || !dev_Bt || !dev_Ct || !dev_Ht || !host_Zt) return set_error(MNT753_EINVAL, "r1cs_qap_at: null argument");
+  if (domain_curve(d) != r->curve) return set_error(MNT753_EINVAL, "r1cs_qap_at: the domain belongs to the other curve");
+  const size_t dm = mnt753_domain_size(d);
+  if (dm < r->nc + r->num_inputs + 1) return set_error(MNT753_EINVAL, "r1cs_qap_at: domain below constraints + inputs + 1");
+  if (r->frm == MOD_A ? host::HFp<MOD_A>::geq_p(host_t) : host::HFp<MOD_B>::geq_p(host_t)) return set_error(MNT753_EINVAL, "r1cs_qap_at: t is not a canonical element of Fr");
+  if (int rc = require_device()) return rc;
+  if (mnt753_domain_device(d) != r->logical_device) return set_error(MNT753_EINVAL, "r1cs_qap_at: the domain and the system live on different devices");
+  if (int rc = qap_prepare(r)) return rc;
+  OnDevice on(r->device);
+  hipStream_t st = (hipStream_t)stream;
+  // qap_u and qap_partial are shared by the calls on this system: a call on another stream starts behind the previous one
+  if (!r->qap_free) HIP_TRY(hipEventCreateWithFlags(&r->qap_free, hipEventDisableTiming));
+  else HIP_TRY(hipStreamWaitEvent(st, r->qap_free, 0));
+  if (r->qap_u_cap < dm) {
+    if (r->qap_u) (void)hipFree(r->qap_u);
+    r->qap_u = nullptr; r->qap_u_cap = 0;
+    if (hipMalloc(&r->qap_u, 96 * dm) != hipSuccess) { (void)hipGetLastError(); r->qap_u = nullptr; return set_error(MNT753_ENOMEM, "r1cs_qap_at: device allocation failed"); }
+    r->qap_u_cap = dm;
+  }
+  uint64_t zt[12];
+  if (int rc = mnt753_domain_vanishing_at(d, host_t, zt)) return rc;
+  if (int rc = mnt753_domain_lagrange_at(d, host_t, reinterpret_cast<uint64_t*>(r->qap_u), stream)) return rc;
+  if (int rc = mnt753_vec_powers(r->curve, host_t, dev_Ht, dm + 1, stream)) return rc;
+  const uint64_t n_chunks = r->qap_plan.work_items, ncols = r->m + 1;
+  const QapMatrices mats = {{r->coeff[0], r->coeff[1], r->coeff[2]}, r->qap_base[1], r->qap_base[2]};
+  uint32_t *at = reinterpret_cast<uint32_t*>(dev_At), *bt = reinterpret_cast<uint32_t*>(dev_Bt), *ct = reinterpret_cast<uint32_t*>(dev_Ct);
+  const unsigned gc = (unsigned)((n_chunks + 255) / 256), gf = (unsigned)((3 * ncols + 255) / 256);
+  if (r->frm == MOD_A) {
+    if (n_chunks) hipLaunchKernelGGL((k_qap_chunks<MOD_A>), dim3(gc), dim3(256), 0, st, mats, r->qap_perm_row, r->qap_perm_k, r->qap_chunk_start, r->qap_chunk_len, r->qap_order, r->qap_u, r->qap_partial, n_chunks);
+    hipLaunchKernelGGL((k_qap_fold<MOD_A>), dim3(gf), dim3(256), 0, st, r->qap_partial, r->qap_col_chunk, r->qap_u, at, bt, ct, ncols, r->nc, r->num_inputs);
+  } else {
+    if (n_chunks) hipLaunchKernelGGL((k_qap_chunks<MOD_B>), dim3(gc), dim3(256), 0, st, mats, r->qap_perm_row, r->qap_perm_k, r->qap_chunk_start, r->qap_chunk_len, r->qap_order, r->qap_u, r->qap_partial, n_chunks);
+    hipLaunchKernelGGL((k_qap_fold<MOD_B>), dim3(gf), dim3(256), 0, st, r->qap_partial, r->qap_col_chunk, r->qap_u, at, bt, ct, ncols, r->nc, r->num_inputs);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(r->qap_free, st));
+  memcpy(host_Zt, zt, 96);
+  return 0;
 }
 
 }  // extern "C"

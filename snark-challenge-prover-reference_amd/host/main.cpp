@@ -1,6 +1,7 @@
 // ./main_hip <curve> compute <params> <input> <output> [<input2> <output2> ...] [--repeat N] [--gpus N] [--fold rccl|host] [--unfused-h] [--unfused-c] [--ref-order] [--quiet]
 //            --serve: keep the parameters resident and prove further "<input> <output>" pairs read from stdin, one per line
 // ./main_hip <curve> compute-r1cs <params> <r1cs> <witness> <output> ...      (ca / cb / cc evaluated on the device from the constraint system)
+// ./main_hip <curve> qap-at <r1cs> <t_file> <output> [--mixed-radix]          (the QAP at the point of <t_file>: At | Bt | Ct | Ht | Zt)
 // ./main_hip <curve> complete <keys> <input|witness> <challenge_proof> <full_proof> [--s-file <Fr> | --s-seed N]
 // ./main_hip <curve> check <params> [<input>] | check-r1cs <params> <r1cs> <witness>      (validation only; exit code 3 = malformed input)
 //            --validate on compute / compute-r1cs / complete: the same checks before proving; a failing job writes nothing
@@ -415,8 +416,82 @@ static int validate_completion(int curve, const char* keys_path, const char* inp
   return 0;
 }
 
+// `main_hip <curve> qap-at <r1cs> <t_file> <output> [--mixed-radix]`: r1cs_to_qap_instance_map_with_evaluation at the point of <t_file>
+// (libsnark/reductions/r1cs_to_qap/r1cs_to_qap.tcc:105-175) on the domain compute-r1cs chooses; writes At | Bt | Ct | Ht | Zt.
+static int qap_at(int curve, const char* r1cs_path, const char* t_path, const char* out_path, bool mixed) {
+  uint64_t t[12];
+  {
+    FILE* f = fopen(t_path, "rb");
+    if (!f) { fprintf(stderr, "main_hip: cannot open %s\n", t_path); return 1; }
+    unsigned char buf[97];
+    const size_t got = fread(buf, 1, sizeof buf, f);
+    fclose(f);
+    if (got != 96) { fprintf(stderr, "main_hip: %s must hold exactly one Fr element (96 bytes)\n", t_path); return 1; }
+    memcpy(t, buf, 96);
+  }
+  ck(mnt753_init(0), "mnt753_init");
+  mnt753_check_report rep;
+  ck(mnt753_check_scalars(curve, t, 0, 1, &rep, nullptr), "mnt753_check_scalars");
+  if (rep.n_bad) { fprintf(stderr, "main_hip: %s: t is not below r\n", t_path); return 1; }
+  // r1cs.bin: u64 num_inputs, m, nc; per matrix a, b, c: u64 row_ptr[nc + 1], u32 col[nnz], Fr coeff[nnz]
+  FILE* f = fopen(r1cs_path, "rb");
+  if (!f) { fprintf(stderr, "main_hip: cannot open %s\n", r1cs_path); return 1; }
+  uint64_t head[3];
+  std::vector<uint64_t> rp[3], cf[3];
+  std::vector<uint32_t> col[3];
+  bool ok = fread(head, 8, 3, f) == 3 && head[2] < ((uint64_t)1 << 40);
+  for (int k = 0; ok && k < 3; ++k) {
+    rp[k].resize(head[2] + 1);
+    ok = fread(rp[k].data(), 8, rp[k].size(), f) == rp[k].size() && rp[k][head[2]] < ((uint64_t)1 << 40);
+    if (!ok) break;
+    const size_t nnz = rp[k][head[2]];
+    col[k].resize(nnz + 1); cf[k].resize(12 * nnz + 12);
+    ok = fread(col[k].data(), 4, nnz, f) == nnz && fread(cf[k].data(), 96, nnz, f) == nnz;
+  }
+  fclose(f);
+  if (!ok) { fprintf(stderr, "main_hip: %s is not a constraint-system file\n", r1cs_path); return 1; }
+  const uint64_t* rpp[3] = {rp[0].data(), rp[1].data(), rp[2].data()};
+  const uint32_t* cp[3] = {col[0].data(), col[1].data(), col[2].data()};
+  const uint64_t* fp[3] = {cf[0].data(), cf[1].data(), cf[2].data()};
+  mnt753_r1cs* r = nullptr;
+  mnt753_domain* d = nullptr;
+  ck(mnt753_r1cs_create(curve, head[0], head[1], head[2], rpp, cp, fp, &r), "mnt753_r1cs_create");
+  ck(mnt753_domain_create_for_ex(curve, mnt753_r1cs_domain_size(r), mixed ? MNT753_DOMAIN_ALLOW_MIXED : 0u, &d), "mnt753_domain_create_for");
+  const size_t nv = head[1] + 1, dm = mnt753_domain_size(d), total = 3 * nv + dm + 1;
+  void* dev = nullptr;
+  ck(mnt753_dev_alloc(&dev, 96 * total), "mnt753_dev_alloc");
+  uint64_t* v = static_cast<uint64_t*>(dev);
+  std::vector<uint64_t> out(12 * (total + 1));
+  ck(mnt753_r1cs_qap_at(r, d, t, v, v + 12 * nv, v + 24 * nv, v + 36 * nv, out.data() + 12 * total, nullptr), "mnt753_r1cs_qap_at");
+  ck(mnt753_sync(nullptr), "mnt753_sync");
+  ck(mnt753_copy_d2h(out.data(), dev, 96 * total), "mnt753_copy_d2h");
+  mnt753_dev_free(dev);
+  mnt753_domain_free(d);
+  mnt753_r1cs_free(r);
+  FILE* o = fopen(out_path, "wb");
+  if (!o) { fprintf(stderr, "main_hip: cannot write %s\n", out_path); return 1; }
+  const bool wrote = fwrite(out.data(), 8, out.size(), o) == out.size();
+  if (fclose(o) != 0 || !wrote) { fprintf(stderr, "main_hip: cannot write %s\n", out_path); return 1; }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   setbuf(stdout, NULL);
+  if (argc >= 3 && !strcmp(argv[2], "qap-at")) {
+    const int curve = !strcmp(argv[1], "MNT4753") ? 0 : (!strcmp(argv[1], "MNT6753") ? 1 : -1);
+    if (curve < 0) { fprintf(stderr, "unknown curve %s\n", argv[1]); return 2; }
+    bool mixed = false;
+    if (const char* e = getenv("MNT753_MIXED_RADIX")) mixed = atoi(e) != 0;
+    std::vector<const char*> pos;
+    for (int i = 3; i < argc; ++i) {
+      if (!strcmp(argv[i], "--mixed-radix")) { mixed = true; continue; }
+      if (argv[i][0] == '-') { fprintf(stderr, "main_hip: unknown option %s\n", argv[i]); return 2; }
+      pos.push_back(argv[i]);
+    }
+    if (pos.size() != 3) { fprintf(stderr, "usage: %s MNT4753|MNT6753 qap-at <r1cs> <t_file> <output> [--mixed-radix]\n", argv[0]); return 2; }
+    try { return qap_at(curve, pos[0], pos[1], pos[2], mixed); }
+    catch (const std::exception& e) { fprintf(stderr, "main_hip: %s\n", e.what()); return 1; }
+  }
   if (argc >= 7 && !strcmp(argv[2], "complete")) {
     const int curve = !strcmp(argv[1], "MNT4753") ? 0 : (!strcmp(argv[1], "MNT6753") ? 1 : -1);
     if (curve < 0) { fprintf(stderr, "unknown curve %s\n", argv[1]); return 2; }
@@ -475,7 +550,8 @@ int main(int argc, char** argv) {
   if (const char* e = getenv("MNT753_MIXED_RADIX")) g_mixed_radix = atoi(e) != 0;
   if (argc < 6) {
     fprintf(stderr, "usage: %s MNT4753|MNT6753 compute <params> <input> <output> [<input2> <output2> ...] [--repeat N] [--serve] [--gpus N] [--tables | --one-shot] [--unfused-h] [--unfused-c] [--ref-order] [--fold rccl|host] [--validate] [--mixed-radix] [--quiet]\n"
-                    "  further (input, output) pairs and --repeat prove against the parameters that are already resident on the GPU\n", argv[0]);
+                    "  further (input, output) pairs and --repeat prove against the parameters that are already resident on the GPU\n"
+                    "       %s MNT4753|MNT6753 qap-at <r1cs> <t_file> <output> [--mixed-radix]\n", argv[0], argv[0]);
     return 2;
   }
   // compute-r1cs <params> <r1cs> <witness> <output>: one more positional argument than compute

@@ -218,6 +218,17 @@ int mnt753_check_products(int curve, const uint64_t* a, const uint64_t* b, const
   stub_report(out, "MNT753_STUB_BAD_ROW", n, MNT753_BAD_UNSATISFIED);
   return 0;
 }
+// the QAP at a point: the stub writes zeros (no arithmetic), with the refusals of the product
+int mnt753_domain_vanishing_at(mnt753_domain* d, const uint64_t* t, uint64_t* zt) { if (!d || !t || !zt) return fail(MNT753_EINVAL, "domain_vanishing_at: null argument"); memset(zt, 0, 96); return 0; }
+int mnt753_domain_lagrange_at(mnt753_domain* d, const uint64_t* t, uint64_t* u, void*) { if (!d || !t || !u) return fail(MNT753_EINVAL, "domain_lagrange_at: null argument"); memset(u, 0, 96 * d->m); return 0; }
+int mnt753_vec_powers(int curve, const uint64_t* t, uint64_t* out, size_t n, void*) { if (curve < 0 || curve > 1 || !t || (n && !out)) return fail(MNT753_EINVAL, "vec_powers: bad argument"); if (n) memset(out, 0, 96 * n); return 0; }
+int mnt753_r1cs_qap_plan(const mnt753_r1cs* r, mnt753_qap_plan* out) { if (!r || !out) return fail(MNT753_EINVAL, "r1cs_qap_plan: null argument"); memset(out, 0, sizeof *out); out->chunk_terms = 256; return 0; }
+int mnt753_r1cs_qap_at(mnt753_r1cs* r, mnt753_domain* d, const uint64_t* t, uint64_t* at, uint64_t* bt, uint64_t* ct, uint64_t* ht, uint64_t* zt, void*) {
+  if (!r || !d || !t || !at || !bt || !ct || !ht || !zt) return fail(MNT753_EINVAL, "r1cs_qap_at: null argument");
+  if (d->m < r->nc + r->num_inputs + 1) return fail(MNT753_EINVAL, "r1cs_qap_at: domain below constraints + inputs + 1");
+  memset(at, 0, 96 * (r->m + 1)); memset(bt, 0, 96 * (r->m + 1)); memset(ct, 0, 96 * (r->m + 1)); memset(ht, 0, 96 * (d->m + 1)); memset(zt, 0, 96);
+  return 0;
+}
 int mnt753_r1cs_check(mnt753_r1cs* r, const uint64_t* w, mnt753_check_report* out, void*) {
   if (!r || !w || !out) return fail(MNT753_EINVAL, "r1cs_check: null argument");
   touch_ro(w, 12 * (r->m + 1));
