@@ -362,6 +362,99 @@ int mnt753_r1cs_qap_plan(const mnt753_r1cs* r, mnt753_qap_plan* out);
 int mnt753_r1cs_qap_at(mnt753_r1cs* r, mnt753_domain* d, const uint64_t* host_t, uint64_t* dev_At, uint64_t* dev_Bt, uint64_t* dev_Ct,
                        uint64_t* dev_Ht, uint64_t* host_Zt, void* stream);
 
+/* ---- Groth16 key generation from given randomness -----------------------------------------------------
+ * swap_AB_if_beneficial (libsnark/relations/constraint_satisfaction_problems/r1cs/r1cs.tcc:194-243): counts the variables (columns
+ * 0 .. m) that a term of a and a term of b touch; if b touches STRICTLY more, a and b change roles inside the system object: the
+ * matrices' device arrays change places and the row work list is renumbered in place, no matrix is copied (a column-major view that
+ * an earlier mnt753_r1cs_qap_at built is dropped and rebuilt by the next one).  *swapped (may be NULL) = 1 if this call exchanged them.
+ * The prover must evaluate the system as it now stands: mnt753_r1cs_evaluate and mnt753_r1cs_qap_at do.  The count reads the column
+ * indices back from the device (4 bytes per term of a and b) and runs on the host; the call blocks. */
+int mnt753_r1cs_swap_ab_if_beneficial(mnt753_r1cs* r, int* swapped);
+/* 1 if a and b stand exchanged relative to the arrays mnt753_r1cs_create was given (an odd number of swaps), else 0 */
+int mnt753_r1cs_is_swapped(const mnt753_r1cs* r);
+
+/* Stable compaction of the non-zero elements of a device vector of n < 2^32 Fr elements (all 12 words zero = zero): dev_compact
+ * receives the non-zero elements in their order, dev_index their strictly increasing original indices, *host_count their number --
+ * the "query density" of r1cs_gg_ppzksnark.tcc:230-244 when the vector is At or Bt.  Three kernels (csrc/keygen_kernels.hip.h): per
+ * workgroup the flags and their count by wave ballots, one workgroup scanning the counts, and the write at ballot-prefix positions;
+ * no atomics, the same output whatever the scheduling.  dev_compact / dev_index may both be NULL: only the count is taken.  Room for n
+ * entries each.  Blocks until *host_count is written.  n = 0: count 0, nothing launched. */
+int mnt753_compact_nonzero(const uint64_t* dev_scalars, size_t n, uint64_t* dev_compact, uint32_t* dev_index, size_t* host_count, void* stream);
+/* dev_out[dev_index[j]] = dev_rows[j] for j < count, rows of row_words u64, and zero words in every other of the n rows of dev_out. */
+int mnt753_scatter_rows(const uint64_t* dev_rows, const uint32_t* dev_index, size_t count, size_t row_words, uint64_t* dev_out, size_t n, void* stream);
+/* mnt753_batch_exp for a vector with many zeros (kc_batch_exp works on a sparse vector for the same reason, knowledge_commitment/
+ * kc_multiexp.tcc): the non-zero scalars are compacted, walked, and their rows scattered back; a zero scalar costs no walk.  The
+ * same words as mnt753_batch_exp writes, everywhere.  Both ends on the device.  *host_count (may be NULL) = non-zero scalars.
+ * count == 0 launches no walk (the output is zeroed); count == n is the plain mnt753_batch_exp on the vector as it lies.  Unlike
+ * mnt753_batch_exp the call allocates its compacted vectors (100 bytes per scalar and one output row per non-zero scalar), blocks on
+ * the count, and returns when the output is complete. */
+int mnt753_batch_exp_sparse(mnt753_fixed_base* fb, const uint64_t* dev_scalars, size_t n, const uint64_t* host_coeff, uint64_t* dev_out_affine,
+                            size_t* host_count, void* stream);
+/* dev_out[i] = (beta At[i] + alpha Bt[i] + Ct[i]) c_i, i < n, c_i = 1 for i <= num_inputs and dinv above: entries 0 .. num_inputs are
+ * the ABC of r1cs_gg_ppzksnark.tcc:257-261, the rest is Lt (:266-273, dinv = delta^-1).  One fused kernel, wire form in and out; beta,
+ * alpha, dinv: canonical Fr elements in HOST memory.  dev_out may be one of the inputs. */
+int mnt753_keygen_combine(int curve, const uint64_t* dev_At, const uint64_t* dev_Bt, const uint64_t* dev_Ct, size_t n, size_t num_inputs,
+                          const uint64_t* host_beta, const uint64_t* host_alpha, const uint64_t* host_dinv, uint64_t* dev_out, void* stream);
+
+/* r1cs_gg_ppzksnark_generator (libsnark/zk_proof_systems/ppzksnark/r1cs_gg_ppzksnark/r1cs_gg_ppzksnark.tcc:212-362) with its
+ * randomness -- t, alpha, beta, delta (:216-219) and the G1 generator (:290) -- turned into arguments: a key is a pure function of
+ * (constraint system, randomness).  The G2 generator is G2::one() (:300), a constant of the library.
+ * mnt753_keygen_sizes: elements of each output for a system and a domain of m_d elements (r1cs_gg_ppzksnark.tcc:281, :318-352;
+ * the challenge's parameter file writes them in this order, generate_parameters.cpp:60-85). */
+typedef struct {
+  uint64_t a_query;      /* m + 1 G1 */
+  uint64_t b_g1_query;   /* m + 1 G1 */
+  uint64_t b_g2_query;   /* m + 1 G2 */
+  uint64_t l_query;      /* m - num_inputs G1 */
+  uint64_t h_query;      /* m_d - 1 G1 */
+  uint64_t abc_g1;       /* num_inputs + 1 G1 */
+} mnt753_keygen_sizes;
+int mnt753_groth16_sizes(const mnt753_r1cs* r, const mnt753_domain* d, mnt753_keygen_sizes* out);
+/* where a key goes: the query vectors on the device (affine wire format, the identity as all-zero words -- write_g1 / write_g2 of
+ * libsnark/serialization.hpp:44-67 -- sized by mnt753_keygen_sizes; each can go straight into mnt753_bases_create(.., on_device = 1, ..)),
+ * the five single elements in host memory (24 words G1, mnt753_affine_words(curve, MNT753_G2) words G2). */
+typedef struct {
+  uint64_t *dev_a_query, *dev_b_g1_query, *dev_b_g2_query, *dev_l_query, *dev_h_query, *dev_abc_g1;
+  uint64_t *host_alpha_g1, *host_beta_g1, *host_beta_g2, *host_delta_g1, *host_delta_g2;
+} mnt753_keygen_out;
+/* Window widths and tiles of the two mnt753_fixed_base objects of a call (0 = the library's default, as for mnt753_fixed_base_create)
+ * and whether a query goes through mnt753_batch_exp_sparse.  By default the queries of At and Bt do, in G1 and in G2 (measured:
+ * DESIGN.md section 4.11 has the figures and the rule); MNT753_KEYGEN_DENSE_G1 / MNT753_KEYGEN_DENSE_G2 walk those vectors as they
+ * lie.  ABC | Lt and Ht always do (Ht has no zero entry, Lt is zero only where a variable is in no constraint).  Arguments of the
+ * call: there is no environment variable and no process-wide setting. */
+#define MNT753_KEYGEN_DENSE_G1 1u
+#define MNT753_KEYGEN_DENSE_G2 2u
+typedef struct {
+  int g1_window_bits, g2_window_bits;
+  size_t g1_tile, g2_tile;
+  unsigned flags, reserved;
+} mnt753_keygen_opts;
+typedef struct {
+  uint64_t non_zero_at, non_zero_bt;   /* the query densities of r1cs_gg_ppzksnark.tcc:230-244 */
+  int swapped;                         /* 1 if this call's swap_AB_if_beneficial exchanged a and b */
+  int reserved;
+} mnt753_keygen_report;
+/* The steps: mnt753_r1cs_swap_ab_if_beneficial (:213; the system object STAYS swapped -- the prover must evaluate the swapped system,
+ * so report->swapped tells), mnt753_r1cs_qap_at (:223), the densities (:230-244), mnt753_keygen_combine (:252-274), Ht cut by two
+ * (:281), the G1 and G2 window tables (:289-307), the five single elements through mnt753_point_scale (:310-314), and mnt753_batch_exp
+ * for At, Bt (G1 and G2), Ht with the coefficient Zt delta^-1, Lt and ABC (:318-352; ABC_0 goes with the rest of ABC through the
+ * table, the same point).  d: a domain of at least nc + num_inputs + 1 elements, any kind mnt753_r1cs_qap_at accepts.  opts may be NULL
+ * (all zero).  The call allocates its tables and vectors, blocks, and returns when every output is complete.
+ * MNT753_EINVAL with nothing enqueued for the key, the system left as it was and no output written -- each a DELIBERATE departure from
+ * the reference, which goes on and writes a useless key (delta = 0 even divides by zero: Fp_model::invert of 0):
+ *   - alpha, beta or delta is zero, or one of t, alpha, beta, delta is >= r;
+ *   - Z(t) = 0, i.e. t lies in the domain (every H entry would be the identity);
+ *   - the G1 generator is the identity or fails mnt753_check_points (that one check kernel does run);
+ * and, as for mnt753_r1cs_qap_at: a null pointer, a domain that is too small, of the other curve or on another device.
+ * The GT element alpha_g1_beta_g2 of a libsnark verification key (:348) needs a pairing, which this library does not have: it is
+ * left to the verifying side. */
+int mnt753_groth16_generate(mnt753_r1cs* r, mnt753_domain* d, const uint64_t* host_t, const uint64_t* host_alpha, const uint64_t* host_beta,
+                            const uint64_t* host_delta, const uint64_t* host_g1_generator, const mnt753_keygen_opts* opts,
+                            const mnt753_keygen_out* out, mnt753_keygen_report* report, void* stream);
+/* G1::one() / G2::one() of the curve in the affine wire format (mnt4753_init.cpp:140-142, :201-203; mnt6753_init.cpp:150-155, :213-219):
+ * the G2 generator mnt753_groth16_generate uses, and the G1 generator `main_hip generate` takes when no randomness file names one. */
+int mnt753_group_generator(int curve, int group, uint64_t* out_affine);
+
 /* ---- input validation (device) --------------------------------------------------------------------------
  * The reference prover trusts its files (unchecked fread, prover_reference_functions.cpp:48-116); what the reference HAS for the
  * purpose is libff's G::is_well_formed() (depends/libff/libff/algebra/curves/mnt753/mnt4753/mnt4753_g1.cpp:348, mnt4753_g2.cpp:371-396,

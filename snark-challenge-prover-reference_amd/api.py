@@ -31,6 +31,31 @@ class CheckReport(C.Structure):
     _fields_ = [("n_bad", C.c_uint64), ("first_bad", C.c_uint64), ("first_reason", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class KeygenSizes(C.Structure):
+    """mnt753_keygen_sizes"""
+    _fields_ = [(k, C.c_uint64) for k in ("a_query", "b_g1_query", "b_g2_query", "l_query", "h_query", "abc_g1")]
+
+
+class KeygenOut(C.Structure):
+    """mnt753_keygen_out"""
+    _fields_ = [(k, C.c_void_p) for k in ("dev_a_query", "dev_b_g1_query", "dev_b_g2_query", "dev_l_query", "dev_h_query", "dev_abc_g1",
+                                          "host_alpha_g1", "host_beta_g1", "host_beta_g2", "host_delta_g1", "host_delta_g2")]
+
+
+class KeygenOpts(C.Structure):
+    """mnt753_keygen_opts"""
+    _fields_ = [("g1_window_bits", C.c_int), ("g2_window_bits", C.c_int), ("g1_tile", C.c_size_t), ("g2_tile", C.c_size_t),
+                ("flags", C.c_uint), ("reserved", C.c_uint)]
+
+
+class KeygenReport(C.Structure):
+    """mnt753_keygen_report"""
+    _fields_ = [("non_zero_at", C.c_uint64), ("non_zero_bt", C.c_uint64), ("swapped", C.c_int), ("reserved", C.c_int)]
+
+
+KEYGEN_DENSE_G1, KEYGEN_DENSE_G2 = 1, 2
+
+
 def lib_path():
     """The product library next to this file; MNT753_LIB names another build of it (development A/B runs: an experimental
     variant is loaded from where it was built instead of being copied over the product file)."""
@@ -129,6 +154,15 @@ def lib():
         "mnt753_fixed_base_table_bytes": (sz, [vp]),
         "mnt753_fixed_base_last_timing": (i, [vp, C.POINTER(C.c_float)]),
         "mnt753_batch_exp": (i, [vp, vp, i, sz, vp, vp, i, vp]),
+        "mnt753_r1cs_swap_ab_if_beneficial": (i, [vp, C.POINTER(C.c_int)]),
+        "mnt753_r1cs_is_swapped": (i, [vp]),
+        "mnt753_compact_nonzero": (i, [vp, sz, vp, vp, C.POINTER(C.c_size_t), vp]),
+        "mnt753_scatter_rows": (i, [vp, vp, sz, sz, vp, sz, vp]),
+        "mnt753_batch_exp_sparse": (i, [vp, vp, sz, vp, vp, C.POINTER(C.c_size_t), vp]),
+        "mnt753_keygen_combine": (i, [i, vp, vp, vp, sz, sz, u64p, u64p, u64p, vp, vp]),
+        "mnt753_groth16_sizes": (i, [vp, vp, C.POINTER(KeygenSizes)]),
+        "mnt753_groth16_generate": (i, [vp, vp, u64p, u64p, u64p, u64p, u64p, C.POINTER(KeygenOpts), C.POINTER(KeygenOut), C.POINTER(KeygenReport), vp]),
+        "mnt753_group_generator": (i, [i, i, u64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)   # AttributeError here = the library does not export what the header declares
@@ -606,6 +640,18 @@ class FixedBase:
         _check(lib().mnt753_batch_exp(self._h, sptr, 1 if on_device else 0, cnt, cptr, optr, out_dev, st), "mnt753_batch_exp")
         return out
 
+    def batch_exp_sparse(self, scalars_ptr, n, out_ptr, coeff=None, stream=None):
+        """mnt753_batch_exp_sparse: batch_exp of a device vector through the compaction of its non-zero scalars; both ends on the
+        device.  Returns the number of non-zero scalars."""
+        kc = None if coeff is None else np.ascontiguousarray(coeff, dtype=np.uint64)
+        assert kc is None or kc.size == 12
+        cptr = C.c_void_p(kc.ctypes.data) if kc is not None else C.c_void_p()
+        st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+        cnt = C.c_size_t(0)
+        _check(lib().mnt753_batch_exp_sparse(self._h, C.c_void_p(int(scalars_ptr)), int(n), cptr, C.c_void_p(int(out_ptr)), C.byref(cnt), st),
+               "mnt753_batch_exp_sparse")
+        return int(cnt.value)
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib().mnt753_fixed_base_free(self._h)
@@ -662,6 +708,23 @@ class R1cs:
         _check(lib().mnt753_r1cs_check(self._h, C.c_void_p(int(dev_w)), C.byref(rep), st), "mnt753_r1cs_check")
         return _report(rep)
 
+    def swap_ab_if_beneficial(self):
+        """swap_AB_if_beneficial of the reference (mnt753_r1cs_swap_ab_if_beneficial): a and b change roles inside the device object if b
+        touches strictly more variables.  Returns True if this call exchanged them; `swapped` tells how the system stands."""
+        flag = C.c_int(0)
+        _check(lib().mnt753_r1cs_swap_ab_if_beneficial(self._h, C.byref(flag)), "mnt753_r1cs_swap_ab_if_beneficial")
+        return bool(flag.value)
+
+    @property
+    def swapped(self):
+        """True if a and b stand exchanged relative to the matrices the object was created from"""
+        return bool(lib().mnt753_r1cs_is_swapped(self._h))
+
+    def host_matrices(self):
+        """the matrices as the device object now holds them: (row_ptr, col, coeff) of a, b, c, with a and b exchanged if `swapped`"""
+        a, b, c = self._keep
+        return [b, a, c] if self.swapped else [a, b, c]
+
     def qap_plan(self):
         """mnt753_r1cs_qap_plan: how qap_at cuts the columns (builds the column-major view if no call has yet)."""
         p = QapPlan()
@@ -696,6 +759,147 @@ class R1cs:
             self.close()
         except Exception:
             pass
+
+
+def write_r1cs_file(path, num_inputs, m, nc, mats):
+    """the inverse of read_r1cs_file"""
+    with open(path, "wb") as f:
+        f.write(np.array([num_inputs, m, nc], dtype="<u8").tobytes())
+        for rp, col, cf in mats:
+            f.write(np.ascontiguousarray(rp, dtype="<u8").tobytes())
+            f.write(np.ascontiguousarray(col, dtype="<u4").tobytes())
+            f.write(np.ascontiguousarray(cf, dtype="<u8").tobytes())
+
+
+def group_generator(curve, group):
+    """G1::one() / G2::one() of the curve in the affine wire format (mnt753_group_generator)"""
+    out = np.zeros(affine_words(curve, group), dtype=np.uint64)
+    _check(lib().mnt753_group_generator(curve, group, out.ctypes.data_as(C.POINTER(C.c_uint64))), "mnt753_group_generator")
+    return out
+
+
+def compact_nonzero(scalars_ptr, n, compact_ptr=None, index_ptr=None, stream=None):
+    """mnt753_compact_nonzero on a device vector of n Fr elements -> the number of non-zero elements; with compact_ptr / index_ptr
+    (device addresses with room for n elements / n uint32) the compacted elements and their indices are written too."""
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    cnt = C.c_size_t(0)
+    cp = C.c_void_p(int(compact_ptr)) if compact_ptr else C.c_void_p()
+    ip = C.c_void_p(int(index_ptr)) if index_ptr else C.c_void_p()
+    _check(lib().mnt753_compact_nonzero(C.c_void_p(int(scalars_ptr)), int(n), cp, ip, C.byref(cnt), st), "mnt753_compact_nonzero")
+    return int(cnt.value)
+
+
+def scatter_rows(rows_ptr, index_ptr, count, row_words, out_ptr, n, stream=None):
+    """mnt753_scatter_rows: out[index[j]] = rows[j], zero words in every other of the n rows of out"""
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    _check(lib().mnt753_scatter_rows(C.c_void_p(int(rows_ptr)), C.c_void_p(int(index_ptr)), int(count), int(row_words), C.c_void_p(int(out_ptr)), int(n), st),
+           "mnt753_scatter_rows")
+
+
+def keygen_combine(curve, at_ptr, bt_ptr, ct_ptr, n, num_inputs, beta, alpha, dinv, out_ptr, stream=None):
+    """mnt753_keygen_combine: out[i] = (beta At[i] + alpha Bt[i] + Ct[i]) c_i, c_i = 1 for i <= num_inputs and dinv above"""
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    (kb, pb), (ka, pa), (kd, pd) = _fr_elem(beta), _fr_elem(alpha), _fr_elem(dinv)
+    _check(lib().mnt753_keygen_combine(curve, C.c_void_p(int(at_ptr)), C.c_void_p(int(bt_ptr)), C.c_void_p(int(ct_ptr)), int(n), int(num_inputs),
+                                       pb, pa, pd, C.c_void_p(int(out_ptr)), st), "mnt753_keygen_combine")
+
+
+class GeneratedKey:
+    """A Groth16 key as mnt753_groth16_generate makes it.  The query vectors stay on the device (`buffers`: DeviceBuffers named
+    A, B1, B2, L, H, ABC); `bases(which)` makes a BaseSet of one without a copy through the host; `write(dir)` writes the files of
+    `main_hip generate`.  `non_zero_at` / `non_zero_bt` are the reference's query densities, `swapped` says whether this call's
+    swap_AB_if_beneficial exchanged a and b (the system the key is for is `r1cs_matrices`, which write() puts into r1cs.bin).
+    from_host() builds the same object around numpy arrays, for writing a key that is already in host memory."""
+
+    QUERIES = (("A", G1), ("B1", G1), ("B2", G2), ("L", G1), ("H", G1), ("ABC", G1))
+
+    def __init__(self, curve, num_inputs, num_variables, num_constraints, domain_size, counts, singles, r1cs_matrices, buffers=None, host=None,
+                 non_zero_at=None, non_zero_bt=None, swapped=False):
+        self.curve, self.num_inputs, self.num_variables, self.num_constraints = curve, int(num_inputs), int(num_variables), int(num_constraints)
+        self.domain_size = int(domain_size)
+        self.counts = dict(counts)              # elements of each query
+        self.singles = dict(singles)            # alpha_g1, beta_g1, beta_g2, delta_g1, delta_g2: numpy words
+        self.r1cs_matrices = r1cs_matrices
+        self.buffers, self._host = buffers or {}, dict(host or {})
+        self.non_zero_at, self.non_zero_bt, self.swapped = non_zero_at, non_zero_bt, bool(swapped)
+
+    @classmethod
+    def from_host(cls, curve, num_inputs, num_variables, num_constraints, domain_size, queries, singles, r1cs_matrices, **kw):
+        """queries: {"A": words, ...} numpy arrays in the affine wire format"""
+        host = {k: np.ascontiguousarray(v, dtype=np.uint64).reshape(-1) for k, v in queries.items()}
+        counts = {k: host[k].size // affine_words(curve, g) for k, g in cls.QUERIES}
+        return cls(curve, num_inputs, num_variables, num_constraints, domain_size, counts, singles, r1cs_matrices, host=host, **kw)
+
+    def query(self, which):
+        """the words of one query in host memory (copied from the device on first use)"""
+        if which not in self._host:
+            group = dict(self.QUERIES)[which]
+            n = self.counts[which] * affine_words(self.curve, group)
+            self._host[which] = self.buffers[which].to_numpy()[:n] if n else np.zeros(0, dtype=np.uint64)
+        return self._host[which]
+
+    def bases(self, which):
+        """a BaseSet over the query `which` ("A", "B1", "B2", "L", "H" or "ABC") as it lies on the device"""
+        group = dict(self.QUERIES)[which]
+        return BaseSet(self.curve, group, self.buffers[which].ptr.value, on_device=True, n=self.counts[which])
+
+    def write(self, out_dir):
+        """params.bin (the challenge layout of generate_parameters.cpp:60-85: u64 d = domain size - 1, u64 m, then A | B1 | B2 | L | H),
+        keys.bin (alpha_g1 | beta_g1 | beta_g2 | delta_g1 | delta_g2, what `main_hip complete` reads), vk_elements.bin (alpha_g1 |
+        beta_g2 | delta_g2 | ABC_g1: a verification key without its GT element, which needs a pairing) and r1cs.bin (the system the
+        key is for: a and b exchanged if the swap fired)."""
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "params.bin"), "wb") as f:
+            f.write(np.array([self.domain_size - 1, self.num_variables], dtype="<u8").tobytes())
+            for which in ("A", "B1", "B2", "L", "H"):
+                f.write(self.query(which).astype("<u8").tobytes())
+        s = self.singles
+        with open(os.path.join(out_dir, "keys.bin"), "wb") as f:
+            for k in ("alpha_g1", "beta_g1", "beta_g2", "delta_g1", "delta_g2"):
+                f.write(np.ascontiguousarray(s[k], dtype="<u8").tobytes())
+        with open(os.path.join(out_dir, "vk_elements.bin"), "wb") as f:
+            for k in ("alpha_g1", "beta_g2", "delta_g2"):
+                f.write(np.ascontiguousarray(s[k], dtype="<u8").tobytes())
+            f.write(self.query("ABC").astype("<u8").tobytes())
+        write_r1cs_file(os.path.join(out_dir, "r1cs.bin"), self.num_inputs, self.num_variables, self.num_constraints, self.r1cs_matrices)
+
+    def close(self):
+        for b in self.buffers.values():
+            b.close()
+        self.buffers = {}
+
+
+def generate(r1cs, domain, t, alpha, beta, delta, g1_generator, g1_window_bits=0, g2_window_bits=0, g1_tile=0, g2_tile=0,
+             sparse_g1=True, sparse_g2=True, stream=None):
+    """mnt753_groth16_generate: the reference's Groth16 generator with its randomness as arguments -- t, alpha, beta, delta (12 uint64
+    each, wire form) and the G1 generator (24 uint64, affine).  The system object is swapped in place if the reference's rule says so.
+    Window widths and tiles of 0 leave the two tables to the library; sparse_g1 / sparse_g2 say whether the G1 queries of At and Bt /
+    the G2 query of Bt go through the compaction of their non-zero scalars (both do by default).  Returns a GeneratedKey."""
+    sizes = KeygenSizes()
+    _check(lib().mnt753_groth16_sizes(r1cs._h, domain._h, C.byref(sizes)), "mnt753_groth16_sizes")
+    counts = {"A": sizes.a_query, "B1": sizes.b_g1_query, "B2": sizes.b_g2_query, "L": sizes.l_query, "H": sizes.h_query, "ABC": sizes.abc_g1}
+    curve = r1cs.curve
+    bufs = {k: DeviceBuffer(8 * affine_words(curve, g) * max(int(counts[k]), 1)) for k, g in GeneratedKey.QUERIES}
+    singles = {k: np.zeros(affine_words(curve, g), dtype=np.uint64)
+               for k, g in (("alpha_g1", G1), ("beta_g1", G1), ("beta_g2", G2), ("delta_g1", G1), ("delta_g2", G2))}
+    out = KeygenOut(*[bufs[k].ptr.value for k, _ in GeneratedKey.QUERIES],
+                    *[singles[k].ctypes.data for k in ("alpha_g1", "beta_g1", "beta_g2", "delta_g1", "delta_g2")])
+    out.dev_l_query = bufs["L"].ptr.value
+    opts = KeygenOpts(int(g1_window_bits), int(g2_window_bits), int(g1_tile), int(g2_tile),
+                      (0 if sparse_g1 else KEYGEN_DENSE_G1) | (0 if sparse_g2 else KEYGEN_DENSE_G2), 0)
+    rep = KeygenReport()
+    (kt, pt), (ka, pa), (kb, pb), (kd, pd) = _fr_elem(t), _fr_elem(alpha), _fr_elem(beta), _fr_elem(delta)
+    g = np.ascontiguousarray(g1_generator, dtype=np.uint64).reshape(-1)
+    assert g.size == 24
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    rc = lib().mnt753_groth16_generate(r1cs._h, domain._h, pt, pa, pb, pd, g.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(opts), C.byref(out),
+                                       C.byref(rep), st)
+    if rc != 0:
+        for b in bufs.values():
+            b.close()
+        _check(rc, "mnt753_groth16_generate")
+    return GeneratedKey(curve, r1cs.num_inputs, r1cs.m, r1cs.nc, domain.m, counts, singles, r1cs.host_matrices(), buffers=bufs,
+                        non_zero_at=int(rep.non_zero_at), non_zero_bt=int(rep.non_zero_bt), swapped=bool(rep.swapped))
 
 
 def test_field_op(mod, op, a, b=None):

@@ -26,6 +26,7 @@
 #include "msm_kernels.hip.h"
 #include "qap_kernels.hip.h"
 #include "qap_transpose.hpp"
+#include "r1cs_api.hpp"
 
 using namespace mnt753;
 
@@ -50,6 +51,7 @@ struct mnt753_r1cs {
   uint32_t* qap_u = nullptr;                            // device, the Lagrange coefficients of the last call's domain (wire form)
   size_t qap_u_cap = 0;
   hipEvent_t qap_free = nullptr;                        // recorded behind every qap_at: the next one (any stream) waits for it before it touches qap_u / qap_partial
+  bool ab_swapped = false;                              // a and b stand exchanged relative to creation (mnt753_r1cs_swap_ab_if_beneficial)
 };
 
 namespace {
@@ -113,6 +115,14 @@ __global__ void __launch_bounds__(256) k_r1cs_evaluate(const uint64_t* __restric
   fp_pack(wv, canon);
   store_wire24(dst, wv);
 }
+// a and b change roles in the work list: item which * nc + row of a becomes b's and the reverse; the order by length stays valid
+__global__ void __launch_bounds__(256) k_r1cs_work_swap_ab(uint64_t* __restrict__ work, uint64_t nc) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 3 * nc) return;
+  const uint64_t item = work[t];
+  if (item < nc) work[t] = item + nc;
+  else if (item < 2 * nc) work[t] = item - nc;
+}
 // the column-major view, once per system: the row-major index arrays come back from the device (mnt753_r1cs_create keeps no host
 // copy: a prover pays nothing for this), the permutation is built on the host and uploaded
 int qap_prepare(const mnt753_r1cs* r) {
@@ -165,6 +175,14 @@ int qap_prepare(const mnt753_r1cs* r) {
   return 0;
 }
 }  // namespace
+
+namespace mnt753 {
+int r1cs_curve(const mnt753_r1cs* r) { return r ? r->curve : -1; }
+int r1cs_device(const mnt753_r1cs* r, int* logical) {
+  if (logical) *logical = r ? r->logical_device : -1;
+  return r ? r->device : -1;
+}
+}  // namespace mnt753
 
 extern "C" {
 
@@ -285,6 +303,53 @@ int mnt753_r1cs_check(mnt753_r1cs* r, const uint64_t* dev_w, mnt753_check_report
   (void)hipFree(scratch);
   return rc;
 }
+
+// swap_AB_if_beneficial (r1cs.tcc:194-243)
+int mnt753_r1cs_swap_ab_if_beneficial(mnt753_r1cs* r, int* swapped) {
+  if (swapped) *swapped = 0;
+  if (!r) return set_error(MNT753_EINVAL, "r1cs_swap_ab_if_beneficial: null argument");
+  if (int rc = require_device()) return rc;
+  OnDevice on(r->device);
+  // r1cs.tcc:199-219: the variables a term of a / of b names, whatever its coefficient
+  uint64_t touched[2] = {0, 0};
+  {
+    std::vector<uint8_t> seen;
+    std::vector<uint32_t> cl;
+    HIP_TRY(hipDeviceSynchronize());     // the arrays may be in use by work enqueued on any stream
+    for (int k = 0; k < 2; ++k) {
+      seen.assign(r->m + 1, 0);
+      cl.resize(r->nnz[k] + 1);
+      if (r->nnz[k]) HIP_TRY(hipMemcpy(cl.data(), r->col[k], 4 * r->nnz[k], hipMemcpyDeviceToHost));
+      for (uint64_t i = 0; i < r->nnz[k]; ++i) seen[cl[i]] = 1;
+      for (uint8_t v : seen) touched[k] += v;
+    }
+  }
+  if (touched[1] <= touched[0]) return 0;       // :228: strictly more
+  if (r->nc) {
+    hipLaunchKernelGGL(k_r1cs_work_swap_ab, dim3((unsigned)((3 * r->nc + 255) / 256)), dim3(256), 0, 0, r->work, r->nc);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  std::swap(r->row_ptr[0], r->row_ptr[1]);
+  std::swap(r->col[0], r->col[1]);
+  std::swap(r->coeff[0], r->coeff[1]);
+  std::swap(r->nnz[0], r->nnz[1]);
+  r->ab_swapped = !r->ab_swapped;
+  {
+    // the column-major view lists a's terms in front of b's: the next mnt753_r1cs_qap_at builds it again
+    std::lock_guard<std::mutex> lock(r->qap_mutex);
+    if (r->qap_built) {
+      void** qap[] = {(void**)&r->qap_perm_row, (void**)&r->qap_perm_k, (void**)&r->qap_chunk_len, (void**)&r->qap_order, (void**)&r->qap_chunk_start,
+                      (void**)&r->qap_col_chunk, (void**)&r->qap_partial};
+      for (void** p : qap) { if (*p) (void)hipFree(*p); *p = nullptr; }
+      r->qap_built = false;
+    }
+  }
+  if (swapped) *swapped = 1;
+  return 0;
+}
+
+int mnt753_r1cs_is_swapped(const mnt753_r1cs* r) { return r && r->ab_swapped ? 1 : 0; }
 
 int mnt753_r1cs_qap_plan(const mnt753_r1cs* r, mnt753_qap_plan* out) {
   if (!r || !out) return set_error(MNT753_EINVAL, "r1cs_qap_plan: null argument");

@@ -2,6 +2,7 @@
 //            --serve: keep the parameters resident and prove further "<input> <output>" pairs read from stdin, one per line
 // ./main_hip <curve> compute-r1cs <params> <r1cs> <witness> <output> ...      (ca / cb / cc evaluated on the device from the constraint system)
 // ./main_hip <curve> qap-at <r1cs> <t_file> <output> [--mixed-radix]          (the QAP at the point of <t_file>: At | Bt | Ct | Ht | Zt)
+// ./main_hip <curve> generate <r1cs> <out_dir> [--randomness <file>] [--mixed-radix]   (a Groth16 key for the system: params.bin, keys.bin, vk_elements.bin, r1cs.bin)
 // ./main_hip <curve> complete <keys> <input|witness> <challenge_proof> <full_proof> [--s-file <Fr> | --s-seed N]
 // ./main_hip <curve> check <params> [<input>] | check-r1cs <params> <r1cs> <witness>      (validation only; exit code 3 = malformed input)
 //            --validate on compute / compute-r1cs / complete: the same checks before proving; a failing job writes nothing
@@ -13,6 +14,10 @@
 // written against the wrapper type B only -- and are instantiated with the MI355X classes.
 // Timing prints follow libsnark/main.cpp:201-270: the window "Total time from input to output" opens after
 // the parameters are loaded and contains input load, compute and output write.
+#include <sys/random.h>
+#include <sys/stat.h>
+
+#include <cerrno>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -416,6 +421,42 @@ static int validate_completion(int curve, const char* keys_path, const char* inp
   return 0;
 }
 
+// r1cs.bin: u64 num_inputs, m, nc; per matrix a, b, c: u64 row_ptr[nc + 1], u32 col[nnz], Fr coeff[nnz]
+struct R1csFile {
+  uint64_t head[3] = {0, 0, 0};
+  std::vector<uint64_t> rp[3], cf[3];
+  std::vector<uint32_t> col[3];
+  bool load(const char* path) {
+    FILE* f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "main_hip: cannot open %s\n", path); return false; }
+    bool ok = fread(head, 8, 3, f) == 3 && head[2] < ((uint64_t)1 << 40);
+    for (int k = 0; ok && k < 3; ++k) {
+      rp[k].resize(head[2] + 1);
+      ok = fread(rp[k].data(), 8, rp[k].size(), f) == rp[k].size() && rp[k][head[2]] < ((uint64_t)1 << 40);
+      if (!ok) break;
+      const size_t nnz = rp[k][head[2]];
+      col[k].resize(nnz + 1); cf[k].resize(12 * nnz + 12);
+      ok = fread(col[k].data(), 4, nnz, f) == nnz && fread(cf[k].data(), 96, nnz, f) == nnz;
+    }
+    fclose(f);
+    if (!ok) fprintf(stderr, "main_hip: %s is not a constraint-system file\n", path);
+    return ok;
+  }
+  // the same layout, the matrices in the order given (1, 0, 2: a and b exchanged)
+  bool store(const char* path, const int order[3]) const {
+    FILE* f = fopen(path, "wb");
+    if (!f) return false;
+    bool ok = fwrite(head, 8, 3, f) == 3;
+    for (int j = 0; ok && j < 3; ++j) {
+      const int k = order[j];
+      const size_t nnz = rp[k][head[2]];
+      ok = fwrite(rp[k].data(), 8, rp[k].size(), f) == rp[k].size() && fwrite(col[k].data(), 4, nnz, f) == nnz && fwrite(cf[k].data(), 96, nnz, f) == nnz;
+    }
+    return (fclose(f) == 0) && ok;
+  }
+};
+
+
 // `main_hip <curve> qap-at <r1cs> <t_file> <output> [--mixed-radix]`: r1cs_to_qap_instance_map_with_evaluation at the point of <t_file>
 // (libsnark/reductions/r1cs_to_qap/r1cs_to_qap.tcc:105-175) on the domain compute-r1cs chooses; writes At | Bt | Ct | Ht | Zt.
 static int qap_at(int curve, const char* r1cs_path, const char* t_path, const char* out_path, bool mixed) {
@@ -433,26 +474,12 @@ static int qap_at(int curve, const char* r1cs_path, const char* t_path, const ch
   mnt753_check_report rep;
   ck(mnt753_check_scalars(curve, t, 0, 1, &rep, nullptr), "mnt753_check_scalars");
   if (rep.n_bad) { fprintf(stderr, "main_hip: %s: t is not below r\n", t_path); return 1; }
-  // r1cs.bin: u64 num_inputs, m, nc; per matrix a, b, c: u64 row_ptr[nc + 1], u32 col[nnz], Fr coeff[nnz]
-  FILE* f = fopen(r1cs_path, "rb");
-  if (!f) { fprintf(stderr, "main_hip: cannot open %s\n", r1cs_path); return 1; }
-  uint64_t head[3];
-  std::vector<uint64_t> rp[3], cf[3];
-  std::vector<uint32_t> col[3];
-  bool ok = fread(head, 8, 3, f) == 3 && head[2] < ((uint64_t)1 << 40);
-  for (int k = 0; ok && k < 3; ++k) {
-    rp[k].resize(head[2] + 1);
-    ok = fread(rp[k].data(), 8, rp[k].size(), f) == rp[k].size() && rp[k][head[2]] < ((uint64_t)1 << 40);
-    if (!ok) break;
-    const size_t nnz = rp[k][head[2]];
-    col[k].resize(nnz + 1); cf[k].resize(12 * nnz + 12);
-    ok = fread(col[k].data(), 4, nnz, f) == nnz && fread(cf[k].data(), 96, nnz, f) == nnz;
-  }
-  fclose(f);
-  if (!ok) { fprintf(stderr, "main_hip: %s is not a constraint-system file\n", r1cs_path); return 1; }
-  const uint64_t* rpp[3] = {rp[0].data(), rp[1].data(), rp[2].data()};
-  const uint32_t* cp[3] = {col[0].data(), col[1].data(), col[2].data()};
-  const uint64_t* fp[3] = {cf[0].data(), cf[1].data(), cf[2].data()};
+  R1csFile sys;
+  if (!sys.load(r1cs_path)) return 1;
+  const uint64_t* head = sys.head;
+  const uint64_t* rpp[3] = {sys.rp[0].data(), sys.rp[1].data(), sys.rp[2].data()};
+  const uint32_t* cp[3] = {sys.col[0].data(), sys.col[1].data(), sys.col[2].data()};
+  const uint64_t* fp[3] = {sys.cf[0].data(), sys.cf[1].data(), sys.cf[2].data()};
   mnt753_r1cs* r = nullptr;
   mnt753_domain* d = nullptr;
   ck(mnt753_r1cs_create(curve, head[0], head[1], head[2], rpp, cp, fp, &r), "mnt753_r1cs_create");
@@ -475,8 +502,122 @@ static int qap_at(int curve, const char* r1cs_path, const char* t_path, const ch
   return 0;
 }
 
+static bool write_words(const std::string& path, const std::vector<std::pair<const uint64_t*, size_t>>& parts) {
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) { fprintf(stderr, "main_hip: cannot write %s\n", path.c_str()); return false; }
+  bool ok = true;
+  for (auto& p : parts) ok = ok && fwrite(p.first, 8, p.second, f) == p.second;
+  if (fclose(f) != 0 || !ok) { fprintf(stderr, "main_hip: cannot write %s\n", path.c_str()); return false; }
+  return true;
+}
+
+// `main_hip <curve> generate <r1cs> <out_dir> [--randomness <file>] [--mixed-radix]`: r1cs_gg_ppzksnark_generator (libsnark/zk_proof_systems/
+// ppzksnark/r1cs_gg_ppzksnark/r1cs_gg_ppzksnark.tcc:212-362) on the device, mnt753_groth16_generate.  The randomness file is t | alpha |
+// beta | delta (4 x 96 bytes) followed by the G1 generator (affine, 192 bytes); without one the four scalars come from the operating
+// system's generator (getrandom, 753-bit draws rejected at r and, for alpha, beta and delta, at zero), the G1 generator is G1::one(),
+// and the scalars are written nowhere.  Files: params.bin (the challenge layout, generate_parameters.cpp:60-85), keys.bin (what
+// `complete` reads), vk_elements.bin (alpha_g1 | beta_g2 | delta_g2 | ABC_g1) and r1cs.bin (the system the key is for: a and b
+// exchanged if swap_AB_if_beneficial fired -- the file compute-r1cs must be given).
+static int generate_key(int curve, const char* r1cs_path, const char* out_dir, const char* rand_path, bool mixed) {
+  uint64_t rnd[4 * 12 + 24];
+  ck(mnt753_init(0), "mnt753_init");
+  if (rand_path) {
+    FILE* f = fopen(rand_path, "rb");
+    if (!f) { fprintf(stderr, "main_hip: cannot open %s\n", rand_path); return 1; }
+    unsigned char buf[sizeof rnd + 1];
+    const size_t got = fread(buf, 1, sizeof buf, f);
+    fclose(f);
+    if (got != sizeof rnd) { fprintf(stderr, "main_hip: %s must hold t | alpha | beta | delta and the G1 generator (%zu bytes)\n", rand_path, sizeof rnd); return 1; }
+    memcpy(rnd, buf, sizeof rnd);
+  } else {
+    for (int k = 0; k < 4; ++k) {
+      for (int tries = 0;; ++tries) {
+        if (tries > 1000) { fprintf(stderr, "main_hip: the system's random generator gives no element below r\n"); return 1; }
+        uint64_t* x = rnd + 12 * k;
+        if (getrandom(x, 96, 0) != 96) { fprintf(stderr, "main_hip: getrandom failed\n"); return 1; }
+        x[11] &= ((uint64_t)1 << (753 - 704)) - 1;      // r has 753 bits
+        mnt753_check_report rep;
+        ck(mnt753_check_scalars(curve, x, 0, 1, &rep, nullptr), "mnt753_check_scalars");
+        bool zero = true;
+        for (int i = 0; i < 12; ++i) zero = zero && x[i] == 0;
+        if (!rep.n_bad && !(zero && k > 0)) break;
+      }
+    }
+    ck(mnt753_group_generator(curve, MNT753_G1, rnd + 48), "mnt753_group_generator");
+  }
+  R1csFile sys;
+  if (!sys.load(r1cs_path)) return 1;
+  if (mkdir(out_dir, 0777) != 0 && errno != EEXIST) { fprintf(stderr, "main_hip: cannot create %s\n", out_dir); return 1; }
+  const uint64_t* rpp[3] = {sys.rp[0].data(), sys.rp[1].data(), sys.rp[2].data()};
+  const uint32_t* cp[3] = {sys.col[0].data(), sys.col[1].data(), sys.col[2].data()};
+  const uint64_t* fp[3] = {sys.cf[0].data(), sys.cf[1].data(), sys.cf[2].data()};
+  mnt753_r1cs* r = nullptr;
+  mnt753_domain* d = nullptr;
+  ck(mnt753_r1cs_create(curve, sys.head[0], sys.head[1], sys.head[2], rpp, cp, fp, &r), "mnt753_r1cs_create");
+  ck(mnt753_domain_create_for_ex(curve, mnt753_r1cs_domain_size(r), mixed ? MNT753_DOMAIN_ALLOW_MIXED : 0u, &d), "mnt753_domain_create_for");
+  mnt753_keygen_sizes sz;
+  ck(mnt753_groth16_sizes(r, d, &sz), "mnt753_groth16_sizes");
+  const size_t w1 = mnt753_affine_words(curve, MNT753_G1), w2 = mnt753_affine_words(curve, MNT753_G2);
+  const size_t words[6] = {w1 * sz.a_query, w1 * sz.b_g1_query, w2 * sz.b_g2_query, w1 * sz.l_query, w1 * sz.h_query, w1 * sz.abc_g1};
+  size_t off[7] = {0};
+  for (int k = 0; k < 6; ++k) off[k + 1] = off[k] + words[k];
+  void* dev = nullptr;
+  ck(mnt753_dev_alloc(&dev, 8 * off[6]), "mnt753_dev_alloc");
+  uint64_t* v = static_cast<uint64_t*>(dev);
+  std::vector<uint64_t> host(off[6] + 1), single(3 * w1 + 2 * w2);
+  uint64_t *alpha_g1 = single.data(), *beta_g1 = alpha_g1 + w1, *beta_g2 = beta_g1 + w1, *delta_g1 = beta_g2 + w2, *delta_g2 = delta_g1 + w1;
+  const mnt753_keygen_out out = {v + off[0], v + off[1], v + off[2], v + off[3], v + off[4], v + off[5], alpha_g1, beta_g1, beta_g2, delta_g1, delta_g2};
+  mnt753_keygen_report rep;
+  const int rc = mnt753_groth16_generate(r, d, rnd, rnd + 12, rnd + 24, rnd + 36, rnd + 48, nullptr, &out, &rep, nullptr);
+  if (rc == MNT753_EINVAL) { fprintf(stderr, "main_hip: %s\n", mnt753_last_error()); return 3; }
+  ck(rc, "mnt753_groth16_generate");
+  ck(mnt753_copy_d2h(host.data(), dev, 8 * off[6]), "mnt753_copy_d2h");
+  const uint64_t d_minus_1 = mnt753_domain_size(d) - 1, header[2] = {d_minus_1, sys.head[1]};
+  mnt753_dev_free(dev);
+  mnt753_domain_free(d);
+  mnt753_r1cs_free(r);
+  const std::string dir(out_dir);
+  const uint64_t* h = host.data();
+  if (!write_words(dir + "/params.bin", {{header, 2}, {h + off[0], words[0]}, {h + off[1], words[1]}, {h + off[2], words[2]}, {h + off[3], words[3]}, {h + off[4], words[4]}}))
+    return 1;
+  if (!write_words(dir + "/keys.bin", {{alpha_g1, w1}, {beta_g1, w1}, {beta_g2, w2}, {delta_g1, w1}, {delta_g2, w2}})) return 1;
+  if (!write_words(dir + "/vk_elements.bin", {{alpha_g1, w1}, {beta_g2, w2}, {delta_g2, w2}, {h + off[5], words[5]}})) return 1;
+  const int as_is[3] = {0, 1, 2}, exchanged[3] = {1, 0, 2};
+  if (!sys.store((dir + "/r1cs.bin").c_str(), rep.swapped ? exchanged : as_is)) { fprintf(stderr, "main_hip: cannot write %s/r1cs.bin\n", out_dir); return 1; }
+  if (!g_quiet)
+    printf("generate: %llu variables, %llu constraints, domain of %llu elements; non-zero At %llu, Bt %llu; a and b %s\n", (unsigned long long)sys.head[1],
+           (unsigned long long)sys.head[2], (unsigned long long)(d_minus_1 + 1), (unsigned long long)rep.non_zero_at, (unsigned long long)rep.non_zero_bt,
+           rep.swapped ? "exchanged" : "as given");
+  return 0;
+}
+
 int main(int argc, char** argv) {
   setbuf(stdout, NULL);
+  if (argc >= 3 && !strcmp(argv[2], "generate")) {
+    const int curve = !strcmp(argv[1], "MNT4753") ? 0 : (!strcmp(argv[1], "MNT6753") ? 1 : -1);
+    if (curve < 0) { fprintf(stderr, "unknown curve %s\n", argv[1]); return 2; }
+    bool mixed = false;
+    if (const char* e = getenv("MNT753_MIXED_RADIX")) mixed = atoi(e) != 0;
+    const char* rand_path = nullptr;
+    std::vector<const char*> pos;
+    for (int i = 3; i < argc; ++i) {
+      if (!strcmp(argv[i], "--mixed-radix")) { mixed = true; continue; }
+      if (!strcmp(argv[i], "--quiet")) { g_quiet = true; continue; }
+      if (!strcmp(argv[i], "--randomness") && i + 1 < argc) { rand_path = argv[++i]; continue; }
+      if (argv[i][0] == '-') { fprintf(stderr, "main_hip: unknown option %s\n", argv[i]); return 2; }
+      pos.push_back(argv[i]);
+    }
+    if (pos.size() != 2) {
+      fprintf(stderr, "usage: %s MNT4753|MNT6753 generate <r1cs> <out_dir> [--randomness <file>] [--mixed-radix] [--quiet]\n"
+                      "  writes params.bin, keys.bin, vk_elements.bin (alpha_g1 | beta_g2 | delta_g2 | ABC_g1) and r1cs.bin into <out_dir>.\n"
+                      "  The GT element alpha_g1_beta_g2 of a libsnark verification key needs a pairing and is left to the verifying side.\n"
+                      "  <file>: t | alpha | beta | delta (4 x 96 bytes) and the G1 generator (affine); without it the scalars are drawn from the\n"
+                      "  operating system's generator and written nowhere, and the G1 generator is the curve's standard one.\n", argv[0]);
+      return 2;
+    }
+    try { return generate_key(curve, pos[0], pos[1], rand_path, mixed); }
+    catch (const std::exception& e) { fprintf(stderr, "main_hip: %s\n", e.what()); return 1; }
+  }
   if (argc >= 3 && !strcmp(argv[2], "qap-at")) {
     const int curve = !strcmp(argv[1], "MNT4753") ? 0 : (!strcmp(argv[1], "MNT6753") ? 1 : -1);
     if (curve < 0) { fprintf(stderr, "unknown curve %s\n", argv[1]); return 2; }

@@ -236,4 +236,29 @@ int mnt753_r1cs_check(mnt753_r1cs* r, const uint64_t* w, mnt753_check_report* ou
   return 0;
 }
 int mnt753_synth_scalars(int, uint64_t seed, size_t n, uint64_t* out) { for (size_t i = 0; i < 12 * n; ++i) out[i] = seed + i; return 0; }
+int mnt753_group_generator(int curve, int group, uint64_t* out) {
+  if (curve < 0 || curve > 1 || (group != MNT753_G1 && group != MNT753_G2) || !out) return fail(MNT753_EINVAL, "group_generator: bad argument");
+  for (size_t i = 0; i < mnt753_affine_words(curve, group); ++i) out[i] = 1 + i;
+  return 0;
+}
+int mnt753_groth16_sizes(const mnt753_r1cs* r, const mnt753_domain* d, mnt753_keygen_sizes* out) {
+  if (!r || !d || !out || d->m < r->nc + r->num_inputs + 1) return fail(MNT753_EINVAL, "groth16_sizes: bad argument");
+  out->a_query = out->b_g1_query = out->b_g2_query = r->m + 1; out->l_query = r->m - r->num_inputs; out->h_query = d->m - 1; out->abc_g1 = r->num_inputs + 1;
+  return 0;
+}
+int mnt753_groth16_generate(mnt753_r1cs* r, mnt753_domain* d, const uint64_t* t, const uint64_t* alpha, const uint64_t* beta, const uint64_t* delta, const uint64_t* g1,
+                            const mnt753_keygen_opts*, const mnt753_keygen_out* out, mnt753_keygen_report* rep, void*) {
+  mnt753_keygen_sizes sz;
+  if (!t || !alpha || !beta || !delta || !g1 || !out) return fail(MNT753_EINVAL, "groth16_generate: null argument");
+  if (int rc = mnt753_groth16_sizes(r, d, &sz)) return rc;
+  touch_ro(t, 12); touch_ro(alpha, 12); touch_ro(beta, 12); touch_ro(delta, 12); touch_ro(g1, 24);
+  const size_t w1 = mnt753_affine_words(d->curve, MNT753_G1), w2 = mnt753_affine_words(d->curve, MNT753_G2);
+  memset(out->dev_a_query, 0, 8 * w1 * sz.a_query); memset(out->dev_b_g1_query, 0, 8 * w1 * sz.b_g1_query); memset(out->dev_b_g2_query, 0, 8 * w2 * sz.b_g2_query);
+  if (sz.l_query) memset(out->dev_l_query, 0, 8 * w1 * sz.l_query);
+  memset(out->dev_h_query, 0, 8 * w1 * sz.h_query); memset(out->dev_abc_g1, 0, 8 * w1 * sz.abc_g1);
+  memset(out->host_alpha_g1, 0, 8 * w1); memset(out->host_beta_g1, 0, 8 * w1); memset(out->host_beta_g2, 0, 8 * w2); memset(out->host_delta_g1, 0, 8 * w1);
+  memset(out->host_delta_g2, 0, 8 * w2);
+  if (rep) { rep->non_zero_at = rep->non_zero_bt = 0; rep->swapped = 0; rep->reserved = 0; }
+  return 0;
+}
 }
