@@ -13,6 +13,7 @@ namespace mnt753 {
 constexpr int FR_OPS = 6;                      // operands per input record
 constexpr int FR_IN_WORDS = FR_OPS * NL;
 constexpr int FR_OUT_WORDS = 2 * NL + 1;
+constexpr int FR_INV_GROUP_LANES = 16;         // FR_INV_GROUP: the group size of the pairing levels (MNT753_PAIR_INV_GROUP)
 
 // op codes (mirrored by tests/field_raw_ref.py).  x0..x5 are the operands, k the scalar argument of the call.
 enum FieldRawOp : int {
@@ -40,6 +41,10 @@ enum FieldRawOp : int {
   FR_FROM_WIRE,        // r0 = fp_from_wire(words 0..23 of x0)
   FR_TO_WIRE,          // words 0..23 of r0 = fp_to_wire(x0)
   FR_NTT2,             // two carry-free butterfly stages of k_ntt_group (below)
+  FR_INV_GROUP = 24,   // device only, whole waves: r0 = x0^-1 through the shared inversion of the pairing levels (fp_inv.hip.h), groups of
+                       // FR_INV_GROUP_LANES consecutive records.  k = 0: fp_inv_lanes, every record its own inverse through ONE inversion
+                       // per group (the residue of fp_inv(x0), canonical limbs not promised); k = 1: fp_inv_group itself, once per record
+                       // of the group on that record's operand in every lane (the limbs of fp_inv(x0), bit for bit)
   FR_NUM_OPS
 };
 

@@ -85,6 +85,35 @@ __global__ void __launch_bounds__(64) k_field_raw(int op, const uint32_t* __rest
   if (i >= n) return;
   field_raw_op<M>(op, in + FR_IN_WORDS * i, k, out + FR_OUT_WORDS * i);
 }
+// FR_INV_GROUP: the lanes of a wave exchange limbs, so every lane of the last wave runs (on the last record again) and the records
+// beyond n are not stored
+template <int M>
+__global__ void __launch_bounds__(64) k_field_raw_inv_group(const uint32_t* __restrict__ in, uint32_t k, uint32_t* __restrict__ out, size_t n) {
+  constexpr int G = FR_INV_GROUP_LANES;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t* rec = in + FR_IN_WORDS * (i < n ? i : n - 1);
+  Fp<M> x, r;
+  for (int l = 0; l < NL; ++l) x.l[l] = rec[l];
+  if (k == 0) {
+    fp_inv_lanes<M, G>(r, x);
+  } else {
+    fp_zero(r);
+    const int lane = (int)(threadIdx.x & 63u);
+#pragma unroll 1
+    for (int s = 0; s < G; ++s) {
+      Fp<M> xs, t;
+      const int src4 = ((lane & ~(G - 1)) + s) << 2;
+#pragma unroll
+      for (int l = 0; l < NL; ++l) xs.l[l] = (uint32_t)__builtin_amdgcn_ds_bpermute(src4, (int)x.l[l]);
+      fp_inv_group<M, G>(t, xs);
+      if ((lane & (G - 1)) == s) r = t;
+    }
+  }
+  if (i >= n) return;
+  uint32_t* o = out + FR_OUT_WORDS * i;
+  for (int l = 0; l < NL; ++l) { o[l] = r.l[l]; o[NL + l] = 0; }
+  o[2 * NL] = 0;
+}
 }  // namespace
 
 extern "C" int mnt753_test_field_raw(int mod, int op, const uint32_t* in, size_t n, uint32_t k, uint32_t* out) {
@@ -97,7 +126,11 @@ extern "C" int mnt753_test_field_raw(int mod, int op, const uint32_t* in, size_t
   HIP_TRY(hipMalloc(&dout.p, sizeof(uint32_t) * FR_OUT_WORDS * n));
   HIP_TRY(hipMemcpy(din.p, in, sizeof(uint32_t) * FR_IN_WORDS * n, hipMemcpyHostToDevice));
   const unsigned g = (unsigned)((n + 63) / 64);
-  if (mod == MOD_A) hipLaunchKernelGGL((k_field_raw<MOD_A>), dim3(g), dim3(64), 0, 0, op, din.p, k, dout.p, n);
+  if (op == FR_INV_GROUP) {
+    if (k > 1) return set_error(MNT753_EINVAL, "test_field_raw: FR_INV_GROUP takes k = 0 or 1");
+    if (mod == MOD_A) hipLaunchKernelGGL((k_field_raw_inv_group<MOD_A>), dim3(g), dim3(64), 0, 0, din.p, k, dout.p, n);
+    else hipLaunchKernelGGL((k_field_raw_inv_group<MOD_B>), dim3(g), dim3(64), 0, 0, din.p, k, dout.p, n);
+  } else if (mod == MOD_A) hipLaunchKernelGGL((k_field_raw<MOD_A>), dim3(g), dim3(64), 0, 0, op, din.p, k, dout.p, n);
   else hipLaunchKernelGGL((k_field_raw<MOD_B>), dim3(g), dim3(64), 0, 0, op, din.p, k, dout.p, n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, dout.p, sizeof(uint32_t) * FR_OUT_WORDS * n, hipMemcpyDeviceToHost));

@@ -462,6 +462,21 @@ int launch_pair_level(mnt753_bases* b, hipStream_t st, uint32_t lanes, const uin
                      reinterpret_cast<uint4*>(b->d_pair_ws), PAIR_MIN_B, lanes, b->d_gen, b->d_fix, irr_src);
   return 0;
 }
+#ifdef MNT753_PAIR_TIMING
+// development: the cycle totals one level kernel left in g_pair_cycles, printed per level (regular and irregular) and cleared
+static void pair_timing_report(hipStream_t st, int l) {
+  unsigned long long h[8], z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  (void)hipStreamSynchronize(st);
+  (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_pair_cycles), sizeof(h));
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pair_cycles), z, sizeof(z));
+  unsigned int slots = 1;
+  (void)hipMemcpyFromSymbol(&slots, HIP_SYMBOL(g_pair_slots), sizeof(slots));
+  const double per = (double)h[3] * (slots ? slots : 1);
+  if (h[3]) fprintf(stderr, "pair level %d: waves %llu slots/wave %u  ticks/slot: forward %.0f (dma issue %.0f, store %.0f)  backward %.0f (dma issue %.0f, store %.0f)  inversion/wave %.0f  share %.4f\n", l, h[3], slots,
+                    (double)h[0] / per, (double)h[4] / per, (double)h[5] / per, (double)h[2] / per, (double)h[6] / per, (double)h[7] / per, (double)h[1] / h[3],
+                    (double)h[1] / (double)(h[0] + h[1] + h[2]));
+}
+#endif
 template <class V, class C>
 int pair_and_accumulate(const MsmPlan& p, size_t n, hipStream_t st, const uint32_t* d_aff, mnt753_bases* b, uint32_t* acc_lanes, uint32_t* acc_T, const uint32_t** acc_offs) {
   if constexpr (V::F::DEG == 1 || V::F::LANES > 1) {
@@ -501,17 +516,7 @@ int pair_and_accumulate(const MsmPlan& p, size_t n, hipStream_t st, const uint32
                                : (last ? launch_pair_level<V, false, true, false> : launch_pair_level<V, false, false, false>);
       if (int rc = level(b, st, lanes, d_aff, src_planes, src_stride, b->d_offsets, p.n_buckets, (uint32_t)(levels - l), out, out_stride, nullptr)) return rc;
 #ifdef MNT753_PAIR_TIMING
-      {
-        unsigned long long h[8], z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_pair_cycles), sizeof(h));
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pair_cycles), z, sizeof(z));
-        unsigned int slots = 1;
-        (void)hipMemcpyFromSymbol(&slots, HIP_SYMBOL(g_pair_slots), sizeof(slots));
-        const double per = (double)h[3] * (slots ? slots : 1);
-        if (h[3]) fprintf(stderr, "pair level %d: waves %llu slots/wave %u  ticks/slot: forward %.0f (dma issue %.0f, store %.0f)  backward %.0f (dma issue %.0f, store %.0f)  inversion/wave %.0f\n", l, h[3], slots,
-                          (double)h[0] / per, (double)h[4] / per, (double)h[5] / per, (double)h[2] / per, (double)h[6] / per, (double)h[7] / per, (double)h[1] / h[3]);
-      }
+      pair_timing_report(st, l);
 #endif
       src_planes = reinterpret_cast<const uint4*>(out);
       src_stride = out_stride;
@@ -533,6 +538,9 @@ int pair_and_accumulate(const MsmPlan& p, size_t n, hipStream_t st, const uint32
       const size_t out_stride = blk_quads((cap / 2 + 1) * (uint64_t)V::F::LANES + 64);
       const auto level = k == irr ? launch_pair_level<V, false, true, true> : launch_pair_level<V, false, false, true>;
       if (int rc = level(b, st, lanes, d_aff, src_planes, src_stride, offs_out, p.n_buckets, 0u, out, out_stride, b->d_irr_src)) return rc;
+#ifdef MNT753_PAIR_TIMING
+      pair_timing_report(st, l);
+#endif
       src_planes = reinterpret_cast<const uint4*>(out);
       src_stride = out_stride;
       last_rows = out;

@@ -714,6 +714,10 @@ constexpr uint32_t PAIR_LDS_BYTES = 4 * PAIR_LDS_WAVE_QUADS * 16;
 // 10.59 -> 11.6 ms each; MNT6753 G2 2^15 unchanged -- profiles/r06/g2_dma_portions_ab.txt)
 constexpr uint32_t PAIR_DMA_STEPS_FIRST = MNT753_PAIR_DMA_FIRST, PAIR_DMA_STEPS_LATER = MNT753_PAIR_DMA_LATER, PAIR_DMA_STEPS_IRR = MNT753_PAIR_DMA_IRR;
 
+// lanes that share one inversion between the sweeps of a base-field level (8, 16 or 32; 0: every lane runs its own fp_inv)
+#ifndef MNT753_PAIR_INV_GROUP
+#define MNT753_PAIR_INV_GROUP 16
+#endif
 #ifdef MNT753_PAIR_TIMING
 // development: cycle totals of k_pair_level per wave (s_memtime): [0] forward, [1] inversion, [2] backward, [3] waves, [4..] ad hoc
 __device__ unsigned long long g_pair_cycles[8];
@@ -1086,7 +1090,12 @@ __global__ void __launch_bounds__(256, MNT753_PAIR_WAVES) k_pair_level(const uin
   E inv;
   PAIR_T(tc1);
   if constexpr (LAZY) { F::norm(tmp, run); run = tmp; }   // signed top limb, (-0.3p, 1.3p) -> [0, 2p) for the inversion
-  F::inv(inv, run);
+  // base fields, every level behind the first: the 64 lanes of the wave are all here (the loops above are wave-uniform; lanes without
+  // slots hold 1), and groups of MNT753_PAIR_INV_GROUP lanes share ONE division-step inversion (fp_inv.hip.h, fp_inv_lanes).  The first
+  // level keeps the per-lane inversion: it is 3.6 % of that level, and with the shared form compiled into it the level's sweeps ran
+  // slower than the inversion got shorter (9.50 -> 9.93 ms at 2^20 points, profiles/r07/inv_group_ab.txt)
+  if constexpr (LN == 1 && !first && MNT753_PAIR_INV_GROUP != 0) fp_inv_lanes<M, MNT753_PAIR_INV_GROUP>(inv, run);
+  else F::inv(inv, run);
   PAIR_T(tc2);
   // ---- backward: individual inverses and the sums (highest slot of the wave first)
   // piece `idx` of the LDS-DMA of iteration `it`: ROW_PIECES row pieces, then the 7 quads of the prefix product

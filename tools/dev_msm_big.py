@@ -8,7 +8,7 @@ pkg = load_package(); pkg.init(0)
 curve = int(os.environ.get("CURVE", 0)); group = int(os.environ.get("GROUP", 1))
 logn = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
-n = 1 << logn
+n = int(os.environ.get("N", 1 << logn))      # N: a point count that is no power of two (the label keeps logn)
 t0 = time.time(); pts = pkg.synth_points(curve, group, 42, n); t1 = time.time()
 sc = pkg.synth_scalars(curve, 43, n); t2 = time.time()
 exp = pkg.synth_expected_msm(curve, group, 42, sc); t3 = time.time()

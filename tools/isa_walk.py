@@ -121,6 +121,9 @@ def main():
             else:
                 k = op.split("_")[2]
                 scc = {"eq": x == y, "lg": x != y, "lt": x < y, "gt": x > y, "le": x <= y, "ge": x >= y}[k]
+        elif op.startswith("s_bitcmp"):             # reads both operands, writes scc only (the step loop tests its counter's low bit)
+            x, y = val(toks[0]), val(toks[1])
+            scc = None if x is None or y is None else ((x >> y) & 1) == (1 if op.startswith("s_bitcmp1") else 0)
         elif op in ("s_andn2_b64", "s_and_b64", "s_or_b64", "s_xor_b64", "s_orn2_b64"):
             x, y = val(toks[1]), val(toks[2])
             res = None
@@ -206,7 +209,7 @@ def main():
                 runs[-1][1] = m; runs[-1][2] += 1
             else:
                 runs.append([m, m, 1])
-        print("executed register moves (first, last, count):", [tuple(r) for r in runs if r[2] >= 4])
+        print("executed register moves:", len(moves), " runs of four or more (first, last, count):", [tuple(r) for r in runs if r[2] >= 4])
     if verbose:
         for t in trace:
             print("   ", t)
