@@ -36,6 +36,9 @@ struct FieldFp {
   static HD void sqr_s(E& r, const E& a) { fp_sqr_s(r, a); }
   static HD void mul_s_ip(E& b, E& a) { fp_mul_s_ip(b, a); }         // b <- a b in place, operands opaque in place (fp753.hip.h)
   static HD void sqr_s_keep(E& r, E& a) { fp_sqr_s_keep(r, a); }
+  // the same two products with a Karatsuba product half: same limbs, 168 fewer multiply-adds, 56 more live words (fp753.hip.h)
+  static HD void mul_s_k(E& r, const E& a, const E& b) { fp_mul_s_k(r, a, b); }
+  static HD void mul_s_ip_k(E& b, E& a) { fp_mul_s_ip_k(b, a); }
   static HD void sub_raw(E& r, const E& a, const E& b) { fp_sub_raw(r, a, b); }
   static HD void addsub_raw(E& r, const E& a, const E& y, bool subtract) { fp_addsub_raw(r, a, y, subtract); }
   static HD void norm(E& r, const E& a) { fp_norm(r, a); }

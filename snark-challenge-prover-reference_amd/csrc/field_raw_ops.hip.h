@@ -45,6 +45,8 @@ enum FieldRawOp : int {
                        // FR_INV_GROUP_LANES consecutive records.  k = 0: fp_inv_lanes, every record its own inverse through ONE inversion
                        // per group (the residue of fp_inv(x0), canonical limbs not promised); k = 1: fp_inv_group itself, once per record
                        // of the group on that record's operand in every lane (the limbs of fp_inv(x0), bit for bit)
+  FR_MUL_S_K,          // r0 = fp_mul_s_k(x0, x1): the limbs of FR_MUL_S           (mirrored by tests/mul_karatsuba_ref.py)
+  FR_MUL_S_IP_K,       // b = x1, a = x0; fp_mul_s_ip_k(b, a); r0 = b, r1 = a after the call: the limbs of FR_MUL_S_IP
   FR_NUM_OPS
 };
 
@@ -109,6 +111,8 @@ HD void field_raw_op(int op, const uint32_t* in, uint32_t k, uint32_t* out) {
     case FR_FROM_WIRE: fp_from_wire(r0, x[0].l); break;
     case FR_TO_WIRE: fp_to_wire(r0.l, x[0]); break;
     case FR_NTT2: field_raw_ntt2<M>(r0, r1, x, k); break;
+    case FR_MUL_S_K: fp_mul_s_k(r0, x[0], x[1]); break;
+    case FR_MUL_S_IP_K: r0 = x[1]; fp_mul_s_ip_k(r0, x[0]); r1 = x[0]; break;
     default: break;
   }
   for (int i = 0; i < NL; ++i) { out[i] = r0.l[i]; out[NL + i] = r1.l[i]; }

@@ -39,7 +39,9 @@ struct Fp {
 // (One level of subtractive Karatsuba on the product half -- 561 + 729 multiply-adds instead of 729 + 729 -- was built and measured in
 // round 3: +14 % in the microbenchmark at one wave per SIMD, nothing in the product's kernels, which have no registers for its 14-entry
 // window of 64-bit sums (profiles/r03/ab_karatsuba.txt, mul_variants_mi355x.txt).  It left the product in round 5; the formulation is
-// kept in tools/experiments/mul_variants.hip.)
+// kept in tools/experiments/mul_variants.hip.  Round 8 brought it back PER CALL SITE, for the signed product only: fp_mul_s_k below,
+// used by the base-field instantiations of k_pair_level (both sweeps, MNT753_PAIR_KARATSUBA in msm_kernels.hip.h) and nowhere else;
+// fp_mul, fp_mul2 / fp_mul3 and the squarings keep the product scanning of this section.)
 // ---- Montgomery product, radix 2^756, two interleaved column accumulators ------------------
 // r = a*b*2^-756 mod p, r < 2p provided a*b < 4p^2 (e.g. a,b < 2p; or a < 4p, b < p).
 // Limbs of a may be up to 2^29 (one un-normalised addition) -- the column bound still holds.
@@ -438,6 +440,88 @@ HD void fp_sqr_s_keep(Fp<M>& r, Fp<M>& a) {
     acc >>= LB;
   }
   r.l[NL - 1] = (uint32_t)acc;
+}
+// ---- the signed product with a Karatsuba product half (round 8; the two sweeps of k_pair_level) --------------------------------------
+// One level of subtractive Karatsuba over 14 + 13 limbs, a = a0 + a1 2^392, b = b0 + b1 2^392:
+//     a b = a0 b0 + [(a0 - a1)(b1 - b0) + a0 b0 + a1 b1] 2^392 + a1 b1 2^784
+// 196 + 196 + 169 = 561 multiply-adds instead of 729; the reduction half (729) is fp_mul_s's.  With lo_k, hi_k, md_k the columns of
+// a0 b0, a1 b1 and (a0 - a1)(b1 - b0), and u_k = lo_k + hi_(k-14) (one chain of at most 14 products, k = 0 .. 38),
+//     column k of a b  =  u_k + u_(k-14) + md_(k-14)
+// so the only state besides the two difference operands (28 words) is a window of the last 14 u_k (28 words).  md_(k-14) accumulates
+// straight onto the running column, u_(k-14) is the start value of the reduction's own chain (which fp_mul_s starts at 0), and u_k is
+// added once: 39 64-bit additions and 27 limb differences are what the 168 multiply-adds are traded for.
+// The columns are the SAME integers as fp_mul_s's, so every m_k and every output limb is the same: the result equals fp_mul_s's limb for
+// limb (tools/host_karatsuba_check.cpp, tests/test_mul_karatsuba_gpu.py).
+// Contract (the one both sweeps of the levels meet, and the one that is tested): one operand with limbs 0..25 in [0, 2^28) and limb 26 in
+// (-2^26, 2^28) -- a normalised element or the output of a signed product, whose top limb is signed and small --, the other with
+// |limb| < 2^29 (one limb-wise difference).  Then |a0_i - a1_i| < 1.25 2^28 (< 2^28 for all but the one limb paired with limb 26),
+// |b1_j - b0_j| < 2^30, and the parts of a column are
+//     |md_(k-14)| < 14.25 2^58 = 57 2^56,  |u_k + u_(k-14)| < 27 2^57 = 54 2^56 (27 limb products),  reduction < 14.4 2^56,  carry < 2^36
+// which sum to less than 125.5 2^56 < 2^63: every partial sum of a column, in whatever order it is taken, is inside int64.
+// Two operands with |limb| < 2^29 each do NOT meet that bound (md alone: 14 2^60).  The accumulators below are unsigned, i.e. sums
+// modulo 2^64, read as signed only where a column is shifted: what the result needs is that the differences fit int32 (|.| < 2^30) and
+// that the COLUMN fits int64 -- fp_mul_s's own bound, 27 2^58 + 14.4 2^56 + 2^36 < 2^63 -- while a partial sum may wrap.  The host
+// checker asserts both readings; a call site with two raw operands would rely on the second one (the levels have none).
+// r may be b: r_j is written in column 27 + j >= 27, the low half of b is last read in column 26, b_14 .. b_26 in column 38 (r_11).
+template <int M>
+HD void fp_mul_s_k_columns(uint32_t* r, const uint32_t* a, const uint32_t* b) {
+  constexpr int H = 14, G = NL - H;              // low half 14 limbs, high half 13
+  int32_t da[H], db[H];
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    da[i] = (int32_t)a[i] - (i < G ? (int32_t)a[H + i] : 0);
+    db[i] = (i < G ? (int32_t)b[H + i] : 0) - (int32_t)b[i];
+  }
+  uint64_t acc = 0, u[H];
+  uint32_t m[NL];
+#pragma unroll
+  for (int k = 0; k < 2 * NL - 1; ++k) {
+    const int j = k - H;                         // the column of the middle term that lands here
+    uint64_t uk = 0, acc2 = 0;
+    if (k < 2 * H - 1) {
+#pragma unroll
+      for (int i = (k < H ? 0 : k - H + 1); i <= (k < H ? k : H - 1); ++i) uk += (uint64_t)((int64_t)(int32_t)a[i] * (int32_t)b[k - i]);
+    }
+    if (j >= 0 && j < 2 * G - 1) {
+#pragma unroll
+      for (int i = (j < G ? 0 : j - G + 1); i <= (j < G ? j : G - 1); ++i) uk += (uint64_t)((int64_t)(int32_t)a[H + i] * (int32_t)b[H + j - i]);
+    }
+    if (j >= 0) acc2 = u[j % H];                 // u_(k-14), before u_k takes its place
+    if (j >= 0 && j < 2 * H - 1) {
+#pragma unroll
+      for (int i = (j < H ? 0 : j - H + 1); i <= (j < H ? j : H - 1); ++i) acc += (uint64_t)((int64_t)da[i] * db[j - i]);
+    }
+    if (k < H + 2 * G - 1) { acc += uk; u[k % H] = uk; }     // u_k exists for k <= 38 (hi_24 = a_26 b_26)
+    if (k < NL) {
+#pragma unroll
+      for (int i = 0; i < k; ++i) acc2 += (uint64_t)m[i] * FPC[M].p[k - i];
+      acc += acc2;
+      m[k] = ((uint32_t)acc * FPC[M].inv) & LMASK;
+      acc += (uint64_t)m[k] * FPC[M].p[0];
+    } else {
+#pragma unroll
+      for (int i = k - NL + 1; i < NL; ++i) acc2 += (uint64_t)m[i] * FPC[M].p[k - i];
+      acc += acc2;
+      r[k - NL] = (uint32_t)acc & LMASK;
+    }
+    acc = (uint64_t)((int64_t)acc >> LB);
+  }
+  r[NL - 1] = (uint32_t)acc;
+}
+// r = a * b * 2^-756, the limbs of fp_mul_s(r, a, b)
+template <int M>
+HD void fp_mul_s_k(Fp<M>& r, const Fp<M>& a_in, const Fp<M>& b_in) {
+  Fp<M> a, b;
+#pragma unroll
+  for (int i = 0; i < NL; ++i) { a.l[i] = (uint32_t)fp_opaque_limb(a_in.l[i]); b.l[i] = (uint32_t)fp_opaque_limb(b_in.l[i]); }
+  fp_mul_s_k_columns<M>(r.l, a.l, b.l);
+}
+// b <- a * b * 2^-756, the limbs of fp_mul_s_ip(b, a); a keeps its value
+template <int M>
+HD void fp_mul_s_ip_k(Fp<M>& b, Fp<M>& a) {
+  fp_opaque_inplace(a);
+  fp_opaque_inplace(b);
+  fp_mul_s_k_columns<M>(b.l, a.l, b.l);
 }
 // limb-wise a - b and a +- b (the sign chosen per lane): no carries, signed limbs
 template <int M>

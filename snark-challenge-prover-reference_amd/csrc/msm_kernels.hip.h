@@ -718,6 +718,18 @@ constexpr uint32_t PAIR_DMA_STEPS_FIRST = MNT753_PAIR_DMA_FIRST, PAIR_DMA_STEPS_
 #ifndef MNT753_PAIR_INV_GROUP
 #define MNT753_PAIR_INV_GROUP 16
 #endif
+// the product half of the base-field levels' signed multiplier (fp753.hip.h, fp_mul_s_k: same limbs, 561 + 729 multiply-adds for
+// 729 + 729).  0: schoolbook everywhere; 1: Karatsuba in the forward sweep's running product; 2: there and in the shared multiplier of
+// the backward step loop; 3: in the backward step loop alone.  Round 8, 2^20-point G1 MSM on MNT4753 against 0, alternating builds
+// (profiles/r08/karatsuba_ab.txt): 1 is SLOWER by 0.75 ms although a forward slot executes 93 instructions fewer and the
+// backward sweep is the parent's opcode for opcode; 3 changes nothing there (-0.5 ms on MNT6753); 2 gains 0.45 ms in ten of ten pairs
+// (344 instructions fewer per backward slot, two more AGPRs -- seven or eight on MNT6753 --, no scratch).  The sum of the parts is not
+// the whole: what the compiler makes of one sweep moves with the code of the other, and only the measurement decides.
+#ifndef MNT753_PAIR_KARATSUBA
+#define MNT753_PAIR_KARATSUBA 2
+#endif
+constexpr bool PAIR_KARATSUBA_FWD = MNT753_PAIR_KARATSUBA == 1 || MNT753_PAIR_KARATSUBA == 2;
+constexpr bool PAIR_KARATSUBA_BWD = MNT753_PAIR_KARATSUBA == 2 || MNT753_PAIR_KARATSUBA == 3;
 #ifdef MNT753_PAIR_TIMING
 // development: cycle totals of k_pair_level per wave (s_memtime): [0] forward, [1] inversion, [2] backward, [3] waves, [4..] ad hoc
 __device__ unsigned long long g_pair_cycles[8];
@@ -1082,7 +1094,11 @@ __global__ void __launch_bounds__(256, MNT753_PAIR_WAVES) k_pair_level(const uin
     tw_a += __builtin_readcyclecounter() - tfa0;
 #endif
     if (kind <= PK_CANCEL) {
-      if constexpr (LAZY) F::mul_s(tmp, run, den); else F::mul(tmp, run, den);
+      // run is the output of a signed product (limbs 0..25 in [0, 2^28), a small signed top limb: |run| < 1.3p) and den one raw
+      // difference (|limb| < 2^29, or a normalised 2y / the constant 1): the operand contract of fp_mul_s_k
+      if constexpr (LAZY && PAIR_KARATSUBA_FWD) F::mul_s_k(tmp, run, den);
+      else if constexpr (LAZY) F::mul_s(tmp, run, den);
+      else F::mul(tmp, run, den);
       run = tmp;
     }
     if constexpr (IRR) { sw_cur = sw_nxt; sw_nxt = sw_nn; }
@@ -1295,7 +1311,10 @@ __global__ void __launch_bounds__(256, MNT753_PAIR_WAVES) k_pair_level(const uin
               F::sub_raw(A, x1, x2);
               break;
           }
-          F::mul_s_ip(B, A);
+          // (Karatsuba form, its operand contract in fp753.hip.h: in every step one operand is a normalised element or the output of a
+          // signed product -- inv, pre, 1 / den, lambda: limbs 0..25 in [0, 2^28), |value| < 1.7p so the signed top limb is below 2^26 --
+          // and the other one raw with |limb| < 2^29: x2 - x1, y2 -+ y1, x1 - x3, or normalised as well)
+          if constexpr (PAIR_KARATSUBA_BWD) F::mul_s_ip_k(B, A); else F::mul_s_ip(B, A);
         }
         F::addsub_raw(B, B, y1, !(kind == PK_ADD && flip));
         F::norm(B, B);
