@@ -10,9 +10,9 @@ LIB   := $(PKG)/libmnt753_hip.so
 # known-answer hooks.  Links against the product library; nothing of the product links against it.
 TESTLIB := $(PKG)/libmnt753_hip_test.so
 
-HIP_SRCS := mnt753_core.hip mnt753_msm.hip msm_sort.hip msm_inst_mnt4g1.hip msm_inst_mnt4g2.hip msm_inst_mnt6g1.hip msm_inst_mnt6g2.hip mnt753_fft.hip mnt753_synth.hip mnt753_r1cs.hip mnt753_exchange.hip mnt753_selftest.hip mnt753_validate.hip mnt753_batch_exp.hip batch_exp_inst_mnt4g1.hip batch_exp_inst_mnt4g2.hip batch_exp_inst_mnt6g1.hip batch_exp_inst_mnt6g2.hip mnt753_keygen.hip
+HIP_SRCS := mnt753_core.hip mnt753_msm.hip msm_sort.hip msm_inst_mnt4g1.hip msm_inst_mnt4g2.hip msm_inst_mnt6g1.hip msm_inst_mnt6g2.hip mnt753_fft.hip mnt753_synth.hip mnt753_r1cs.hip mnt753_exchange.hip mnt753_selftest.hip mnt753_validate.hip mnt753_batch_exp.hip batch_exp_inst_mnt4g1.hip batch_exp_inst_mnt4g2.hip batch_exp_inst_mnt6g1.hip batch_exp_inst_mnt6g2.hip mnt753_keygen.hip mnt753_pairing.hip
 HIP_OBJS := $(addprefix $(BUILD)/,$(HIP_SRCS:.hip=.o))
-TEST_SRCS := mnt753_testhooks.hip mnt753_synth_points.hip
+TEST_SRCS := mnt753_testhooks.hip mnt753_synth_points.hip mnt753_pairing_testhooks.hip
 TEST_OBJS := $(addprefix $(BUILD)/,$(TEST_SRCS:.hip=.o))
 HDRS := $(wildcard $(CSRC)/*.hpp $(CSRC)/*.hip.h $(CSRC)/*.h include/*.h)
 
@@ -20,12 +20,17 @@ HOST := $(PKG)/host
 MAIN := $(PKG)/main_hip
 
 LAZY_TEST := $(PKG)/lazy_c_test
+PAIRING_TEST := $(PKG)/pairing_wrapper_test
 
-all: $(LIB) $(TESTLIB) $(MAIN) $(LAZY_TEST) oracle
+all: $(LIB) $(TESTLIB) $(MAIN) $(LAZY_TEST) $(PAIRING_TEST) oracle
 
 # the wrapper's expression fusion from the caller's side (tools/host_tests/lazy_c_test.cpp; run by tests/test_prover_gpu.py)
 $(LAZY_TEST): tools/host_tests/lazy_c_test.cpp $(HOST)/prover_hip_functions.cpp include/prover_hip_functions.hpp include/mnt753_hip.h $(LIB)
 	g++ -O2 -std=c++17 -pthread -o $@ tools/host_tests/lazy_c_test.cpp $(HOST)/prover_hip_functions.cpp -L$(PKG) -lmnt753_hip -Wl,-rpath,'$$ORIGIN'
+
+# B::pairing / B::verify from the caller's side (tools/host_tests/pairing_wrapper_test.cpp; run by tests/test_pairing_gpu.py)
+$(PAIRING_TEST): tools/host_tests/pairing_wrapper_test.cpp $(HOST)/prover_hip_functions.cpp include/prover_hip_functions.hpp include/mnt753_hip.h $(LIB)
+	g++ -O2 -std=c++17 -pthread -o $@ tools/host_tests/pairing_wrapper_test.cpp $(HOST)/prover_hip_functions.cpp -L$(PKG) -lmnt753_hip -Wl,-rpath,'$$ORIGIN'
 
 $(MAIN): $(HOST)/main.cpp $(HOST)/prover_hip_functions.cpp include/prover_hip_functions.hpp include/mnt753_hip.h $(LIB)
 	g++ -O2 -std=c++17 -pthread -o $@ $(HOST)/main.cpp $(HOST)/prover_hip_functions.cpp -L$(PKG) -lmnt753_hip -Wl,-rpath,'$$ORIGIN'
@@ -53,17 +58,21 @@ oracle:
 # Host-only sanitizer builds (no GPU needed, GPU sanitizers do not exist on the pool): main.cpp + the wrapper over a TEST STUB of the
 # C ABI (tools/stub_abi: host memory, no arithmetic) under ASan + UBSan and under TSan.  tests/test_sanitizers_cpu.py runs them.
 SAN_SRCS := $(HOST)/main.cpp $(HOST)/prover_hip_functions.cpp tools/stub_abi/stub_mnt753.cpp
-asan: $(BUILD)/san/main_hip_asan
+asan: $(BUILD)/san/main_hip_asan $(BUILD)/san/host_pairing_check_asan
 tsan: $(BUILD)/san/main_hip_tsan
 $(BUILD)/san/main_hip_asan: $(SAN_SRCS) include/prover_hip_functions.hpp include/mnt753_hip.h
 	@mkdir -p $(BUILD)/san
 	g++ -O1 -g -std=c++17 -pthread -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ $(SAN_SRCS)
+# the tower and the pairing through the one-lane fields on the host (tools/host_pairing_check.cpp), a stand-alone program: run it directly
+$(BUILD)/san/host_pairing_check_asan: tools/host_pairing_check.cpp $(HDRS)
+	@mkdir -p $(BUILD)/san
+	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ tools/host_pairing_check.cpp
 $(BUILD)/san/main_hip_tsan: $(SAN_SRCS) include/prover_hip_functions.hpp include/mnt753_hip.h
 	@mkdir -p $(BUILD)/san
 	g++ -O1 -g -std=c++17 -pthread -fsanitize=thread -o $@ $(SAN_SRCS)
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(TESTLIB) $(MAIN) $(LAZY_TEST)
+	rm -rf $(BUILD) $(LIB) $(TESTLIB) $(MAIN) $(LAZY_TEST) $(PAIRING_TEST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean asan tsan

@@ -446,14 +446,71 @@ typedef struct {
  *   - Z(t) = 0, i.e. t lies in the domain (every H entry would be the identity);
  *   - the G1 generator is the identity or fails mnt753_check_points (that one check kernel does run);
  * and, as for mnt753_r1cs_qap_at: a null pointer, a domain that is too small, of the other curve or on another device.
- * The GT element alpha_g1_beta_g2 of a libsnark verification key (:348) needs a pairing, which this library does not have: it is
- * left to the verifying side. */
+ * The GT element alpha_g1_beta_g2 of a libsnark verification key (:348) is a pairing of two of the outputs: mnt753_vk_create below
+ * computes it from alpha_g1 and beta_g2 and mnt753_vk_serialize writes the complete key (`main_hip <curve> vk`). */
 int mnt753_groth16_generate(mnt753_r1cs* r, mnt753_domain* d, const uint64_t* host_t, const uint64_t* host_alpha, const uint64_t* host_beta,
                             const uint64_t* host_delta, const uint64_t* host_g1_generator, const mnt753_keygen_opts* opts,
                             const mnt753_keygen_out* out, mnt753_keygen_report* report, void* stream);
 /* G1::one() / G2::one() of the curve in the affine wire format (mnt4753_init.cpp:140-142, :201-203; mnt6753_init.cpp:150-155, :213-219):
  * the G2 generator mnt753_groth16_generate uses, and the G1 generator `main_hip generate` takes when no randomness file names one. */
 int mnt753_group_generator(int curve, int group, uint64_t* out_affine);
+
+/* ---- the pairing and Groth16 verification -------------------------------------------------------------
+ * The reduced flipped ate pairing of the curve: replaces libff's mnt{4,6}753_ate_reduced_pairing (depends/libff/libff/algebra/curves/
+ * mnt753/mnt4753/mnt4753_pairing.cpp:681-688: ate_precompute_G1 / _G2, ate_miller_loop, final_exponentiation), for a batch.
+ * GT element: an element of Fq4 = Fq2[v]/(v^2 - u) (MNT4753) or Fq6 = Fq3[v]/(v^2 - u) (MNT6753) as c0 | c1, each an Fq2 / Fq3 element
+ * in the wire form of a G2 coordinate: mnt753_gt_words(curve) = 48 / 72 words, what operator<< writes under BINARY_OUTPUT and
+ * MONTGOMERY_OUTPUT. */
+size_t mnt753_gt_words(int curve);
+/* out_gt[i] = e(g1_affine[i], g2_affine[i]) for i < n: affine wire-format points; on_device != 0: the three pointers are device
+ * pointers.  One lane group (2 or 3 lanes) per pairing; the call blocks until out_gt is complete.  Both arguments go through
+ * mnt753_check_points first: a non-canonical coordinate or a point off its curve is MNT753_EINPUT and nothing is computed (no
+ * subgroup test for G2, as there).  The identity in either argument gives GT one -- a DELIBERATE departure from libff, whose
+ * precomputation runs on the identity's coordinates and returns a value without meaning. */
+int mnt753_pairing(int curve, const uint64_t* g1_affine, const uint64_t* g2_affine, size_t n, int on_device, uint64_t* out_gt, void* stream);
+/* A Groth16 verification key on the device: the counterpart of libsnark's r1cs_gg_ppzksnark_verifier_process_vk
+ * (r1cs_gg_ppzksnark.tcc:499-512).  alpha_g1, beta_g2, delta_g2, abc_g1 (num_inputs + 1 points): affine wire form in host memory --
+ * the contents of `generate`'s vk_elements.bin.  Computes e(alpha_g1, beta_g2) on the device and keeps delta_g2, G2::one() and ABC
+ * there, and -- as libsnark's precompute_G2 does for vk_generator_g2_precomp and vk_delta_g2_precomp -- the Miller-loop coefficients of
+ * G2::one() and delta_g2 (H, 4C, J, L of every doubling step, L1, RZ of every addition step: mnt753_vk_coefficient_bytes, 0.83 MB on
+ * MNT4753 and 1.25 MB on MNT6753 for both points), computed once by one lane group each; every proof's lane group reads them from the
+ * key.  MNT753_EINVAL: an element is the identity; MNT753_EINPUT: an element is non-canonical or off its curve.  The key lives on the
+ * device that is current when it is created. */
+typedef struct mnt753_vk mnt753_vk;
+int mnt753_vk_create(int curve, const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* delta_g2, const uint64_t* abc_g1, size_t num_inputs,
+                     mnt753_vk** out);
+int mnt753_vk_destroy(mnt753_vk* vk);
+size_t mnt753_vk_num_inputs(const mnt753_vk* vk);
+size_t mnt753_vk_coefficient_bytes(const mnt753_vk* vk);   /* device memory of the stored coefficients of the key's two G2 points */
+/* The device memory a mnt753_groth16_verify call on this key may allocate for a chunk of proofs, in bytes: the batch runs in chunks of
+ * cap / (194 + 96 num_inputs) proofs (host-memory batches: 8 proof words + 96 num_inputs more per proof for the staged copy), at
+ * least one and at most 2^16.  0 (the default): chunks of 2^16 proofs. */
+int mnt753_vk_set_workspace_cap(mnt753_vk* vk, size_t bytes);
+/* alpha_g1_beta_g2 of the key, mnt753_gt_words words */
+int mnt753_vk_gt(const mnt753_vk* vk, uint64_t* out);
+/* The bytes the reference writes for r1cs_gg_ppzksnark_verification_key (operator<<, r1cs_gg_ppzksnark.tcc:99-106) when built with
+ * BINARY_OUTPUT, MONTGOMERY_OUTPUT and NO_PT_COMPRESSION: GT | '0' delta_g2 | '0' ABC_g1[0] | the sparse_vector of the rest (domain
+ * size, number of indices, the indices, number of values, each followed by a newline, then '0' ABC_g1[j] for j >= 1).  *len = the
+ * size; buf == NULL asks for the size alone, cap < *len is MNT753_EINVAL. */
+int mnt753_vk_serialize(const mnt753_vk* vk, uint8_t* buf, size_t cap, size_t* len);
+/* out_affine[i] = ABC_g1[0] + sum_j inputs[i][j] ABC_g1[j + 1] for i < n (inputs: n x num_inputs Fr, host memory; out: n G1 points,
+ * affine wire form, the identity as zero words): the accumulation of r1cs_gg_ppzksnark_online_verifier_weak_IC (:522-525).  One lane
+ * per proof, a joint double-and-add over the bits of its inputs: 753 doublings and on average 753 num_inputs / 2 additions in that
+ * lane -- meant for the handful of public inputs of this project's systems, not for thousands.  MNT753_EINPUT: an input is >= r. */
+int mnt753_vk_accumulate(const mnt753_vk* vk, const uint64_t* inputs, size_t n, uint64_t* out_affine);
+/* Verifies n proofs against the key: r1cs_gg_ppzksnark_online_verifier_weak_IC (:515-567) per proof, one lane group each.
+ * proofs: n x (A | B | C), affine wire form, the layout `complete` writes; inputs: n x num_inputs Fr (without the leading 1);
+ * on_device != 0: both are device pointers.  verdicts (host memory, n bytes): 0 accepted, 1 malformed, 2 the pairing check failed.
+ * Malformed: a non-canonical coordinate, a point off its curve, the identity as A, B, C or as the accumulated input point, an input
+ * >= r; such a proof runs the arithmetic on stand-in points, its neighbours in the wave are not disturbed.  The check is
+ * FE(ML(A, B) ML(-acc, G2::one()) ML(-C, delta_g2)) == alpha_g1_beta_g2: one Miller loop over three pairs and one final
+ * exponentiation; the same verdict as the reference's form (:409-414), from which it differs by a factor the final exponentiation
+ * maps to one.  Subgroup membership of B is NOT checked, as in the reference.  Returns the number of proofs not
+ * accepted (>= 0), or a negative MNT753_E* code.  The batch runs in chunks under mnt753_vk_set_workspace_cap (by default 2^16 proofs:
+ * at most 2^16 (194 + 96 num_inputs) bytes, plus the staged copy of a chunk that arrives in host memory); one allocation of each
+ * buffer per call.  With on_device, proofs and inputs must lie on the key's device (MNT753_EINVAL otherwise).  Only B is stepped
+ * through the Miller loop; the coefficients of G2::one() and delta_g2 are read from the key.  Blocks until verdicts is complete. */
+int mnt753_groth16_verify(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int on_device, uint8_t* verdicts, void* stream);
 
 /* ---- input validation (device) --------------------------------------------------------------------------
  * The reference prover trusts its files (unchecked fread, prover_reference_functions.cpp:48-116); what the reference HAS for the

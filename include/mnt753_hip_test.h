@@ -60,6 +60,17 @@ int mnt753_test_ext_raw(int curve, int split, int op, const uint32_t* a, const u
  *       reduction and the levels of the edge merge of a short lane list; split = 0 only). */
 int mnt753_test_point_op(int curve, int group, int split, int op, const uint64_t* p_proj, const uint64_t* q_proj, size_t n, uint64_t* out_proj);
 
+/* The target field of the pairing on the device (csrc/tower753.hip.h), element-wise on n pairs of elements in wire form (c0 | c1,
+ * each an Fq2 / Fq3 element: mnt753_gt_words words; host pointers): Fq4 = Fq2[v]/(v^2 - u) on MNT4753 (depends/libff/libff/algebra/
+ * fields/fp4.tcc), Fq6 = Fq3[v]/(v^2 - u) on MNT6753 (fp6_2over3.tcc).  split: 0 = over the one-lane coordinate field, 1 = over the
+ * lane-split one, which the pairing kernels run.
+ * op: 0 a*b, 1 a*a (complex squaring), 2 a^-1 (0 -> 0), 3 the unitary inverse, 4 a^|w0| (the power of the final exponent's last
+ * chunk), 5 the whole final exponentiation of a, 10 + i the Frobenius map a^(q^i) for 1 <= i < k (k = 4 / 6). */
+int mnt753_test_tower_op(int curve, int split, int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);
+/* The UNREDUCED Miller value of n pairs (affine wire-format points, neither the identity; host pointers): what
+ * mnt{4,6}753_ate_miller_loop returns before final_exponentiation, mnt753_gt_words words per pair. */
+int mnt753_test_miller_loop(int curve, int split, const uint64_t* g1_affine, const uint64_t* g2_affine, size_t n, uint64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <memory>
+#include <vector>
 
 namespace mnt753_hip_detail {
 struct DeviceBuffer;   // RAII hipMalloc'd block
@@ -160,6 +161,12 @@ public:
   static const char *check_reason_text(int reason);
   // seconds the background loader of read_input needed until the whole input file was on the device (waits for it)
   static double input_load_seconds(groth16_input *input);
+  // The pairing and Groth16 verification on the device (mnt753_pairing, mnt753_vk_create + mnt753_groth16_verify): extensions, the
+  // reference's B has neither.  Wire words in host memory.  pairing: n reduced pairings, mnt753_gt_words words each.  verify:
+  // vk_elements = alpha_g1 | beta_g2 | delta_g2 | ABC_g1 (num_inputs + 1 points, the contents of `generate`'s vk_elements.bin),
+  // proofs = n x (A | B | C), inputs = n x num_inputs Fr; one verdict per proof: 0 accepted, 1 malformed, 2 the pairing check failed.
+  static std::vector<uint64_t> pairing(const uint64_t *g1_affine, const uint64_t *g2_affine, size_t n);
+  static std::vector<uint8_t> verify(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *proofs, const uint64_t *inputs, size_t n);
   // raw access for tests / tools
   static const uint64_t *G1_words(const G1 *a);
   static const uint64_t *G2_words(const G2 *a);

@@ -163,6 +163,17 @@ def lib():
         "mnt753_groth16_sizes": (i, [vp, vp, C.POINTER(KeygenSizes)]),
         "mnt753_groth16_generate": (i, [vp, vp, u64p, u64p, u64p, u64p, u64p, C.POINTER(KeygenOpts), C.POINTER(KeygenOut), C.POINTER(KeygenReport), vp]),
         "mnt753_group_generator": (i, [i, i, u64p]),
+        "mnt753_gt_words": (sz, [i]),
+        "mnt753_pairing": (i, [i, vp, vp, sz, i, vp, vp]),
+        "mnt753_vk_create": (i, [i, u64p, u64p, u64p, u64p, sz, C.POINTER(vp)]),
+        "mnt753_vk_destroy": (i, [vp]),
+        "mnt753_vk_num_inputs": (sz, [vp]),
+        "mnt753_vk_coefficient_bytes": (sz, [vp]),
+        "mnt753_vk_set_workspace_cap": (i, [vp, sz]),
+        "mnt753_vk_gt": (i, [vp, u64p]),
+        "mnt753_vk_serialize": (i, [vp, vp, sz, C.POINTER(C.c_size_t)]),
+        "mnt753_vk_accumulate": (i, [vp, u64p, sz, u64p]),
+        "mnt753_groth16_verify": (i, [vp, vp, vp, sz, i, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)   # AttributeError here = the library does not export what the header declares
@@ -199,6 +210,8 @@ def test_lib():
         "mnt753_test_point_op": (i, [i, i, i, i, u64p, u64p, sz, u64p]),
         "mnt753_test_field_raw": (i, [i, i, u32p, sz, C.c_uint32, u32p]),
         "mnt753_test_ext_raw": (i, [i, i, i, u32p, u32p, sz, u32p]),
+        "mnt753_test_tower_op": (i, [i, i, i, u64p, u64p, sz, u64p]),
+        "mnt753_test_miller_loop": (i, [i, i, u64p, u64p, sz, u64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -843,6 +856,11 @@ class GeneratedKey:
         group = dict(self.QUERIES)[which]
         return BaseSet(self.curve, group, self.buffers[which].ptr.value, on_device=True, n=self.counts[which])
 
+    def verification_key(self):
+        """the VerificationKey of this key: alpha_g1, beta_g2, delta_g2 and the ABC query (copied from the device)"""
+        s = self.singles
+        return VerificationKey(self.curve, s["alpha_g1"], s["beta_g2"], s["delta_g2"], self.query("ABC"))
+
     def write(self, out_dir):
         """params.bin (the challenge layout of generate_parameters.cpp:60-85: u64 d = domain size - 1, u64 m, then A | B1 | B2 | L | H),
         keys.bin (alpha_g1 | beta_g1 | beta_g2 | delta_g1 | delta_g2, what `main_hip complete` reads), vk_elements.bin (alpha_g1 |
@@ -969,3 +987,126 @@ def mont_one(curve):
          0x0001c4c62d92c41110229022eee2cdadb7f997505b8fafed5eb7e8f96c97d87307fdb925e8a0ed8d99d124d9a15af79db117e776f218059db80f0da5cb537e38685acce9767254a4638810719ac425f0e39d54522cdd119f5e9063de245e8001][curve]
     v = (1 << 768) % r
     return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(12)], dtype=np.uint64)
+
+
+# ---- the pairing and Groth16 verification -----------------------------------------------------------------------------------------
+def gt_words(curve):
+    return int(lib().mnt753_gt_words(curve))
+
+
+def pairing(curve, P, Q, on_device=False, n=None, out=None, stream=None):
+    """mnt753_pairing: e(P[i], Q[i]) for affine wire-format points -> numpy words [n, gt_words] (host arrays), or into the device
+    address `out` with on_device.  A malformed point raises Mnt753Error; the identity in either argument gives GT one."""
+    p1, cnt, keep1 = _input_ptr(P, on_device, 24, n)
+    p2, cnt2, keep2 = _input_ptr(Q, on_device, affine_words(curve, G2), n)
+    if cnt != cnt2:
+        raise Mnt753Error("pairing: as many G1 as G2 points")
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    if on_device:
+        _check(lib().mnt753_pairing(curve, p1, p2, cnt, 1, C.c_void_p(int(out)), st), "mnt753_pairing")
+        return None
+    res = np.zeros((cnt, gt_words(curve)), dtype=np.uint64)
+    _check(lib().mnt753_pairing(curve, p1, p2, cnt, 0, C.c_void_p(res.ctypes.data), st), "mnt753_pairing")
+    return res
+
+
+class VerificationKey:
+    """mnt753_vk: a Groth16 verification key on the device.  alpha_g1, beta_g2, delta_g2: affine wire words; abc_g1: num_inputs + 1
+    G1 points.  from_elements() takes the contents of `generate`'s vk_elements.bin."""
+
+    def __init__(self, curve, alpha_g1, beta_g2, delta_g2, abc_g1):
+        self.curve = curve
+        a, pa = _u64(alpha_g1)
+        b, pb = _u64(beta_g2)
+        d, pd = _u64(delta_g2)
+        abc, pabc = _u64(np.asarray(abc_g1).reshape(-1))
+        if a.size != 24 or b.size != affine_words(curve, G2) or d.size != b.size or abc.size < 24 or abc.size % 24:
+            raise Mnt753Error("VerificationKey: element sizes do not fit the curve")
+        self.num_inputs = abc.size // 24 - 1
+        self._h = C.c_void_p()
+        _check(lib().mnt753_vk_create(curve, pa, pb, pd, pabc, self.num_inputs, C.byref(self._h)), "mnt753_vk_create")
+
+    @classmethod
+    def from_elements(cls, curve, words):
+        """words: alpha_g1 | beta_g2 | delta_g2 | ABC_g1 (vk_elements.bin)"""
+        w = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+        w2 = affine_words(curve, G2)
+        return cls(curve, w[:24], w[24:24 + w2], w[24 + w2:24 + 2 * w2], w[24 + 2 * w2:])
+
+    def gt(self):
+        out = np.zeros(gt_words(self.curve), dtype=np.uint64)
+        _check(lib().mnt753_vk_gt(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))), "mnt753_vk_gt")
+        return out
+
+    def coefficient_bytes(self):
+        """device memory of the stored Miller-loop coefficients of G2::one() and delta_g2"""
+        return int(lib().mnt753_vk_coefficient_bytes(self._h))
+
+    def set_workspace_cap(self, nbytes):
+        """bytes a verify() call may allocate for a chunk of proofs (0: the default chunk of 2^16 proofs)"""
+        _check(lib().mnt753_vk_set_workspace_cap(self._h, int(nbytes)), "mnt753_vk_set_workspace_cap")
+
+    def serialize(self):
+        """the bytes of the reference's vk.txt"""
+        ln = C.c_size_t()
+        _check(lib().mnt753_vk_serialize(self._h, None, 0, C.byref(ln)), "mnt753_vk_serialize")
+        buf = (C.c_uint8 * ln.value)()
+        _check(lib().mnt753_vk_serialize(self._h, C.cast(buf, C.c_void_p), ln.value, C.byref(ln)), "mnt753_vk_serialize")
+        return bytes(buf)
+
+    def accumulate(self, inputs):
+        """inputs: [n, num_inputs, 12] Fr words -> [n, 24]: ABC[0] + sum_j inputs[i][j] ABC[j + 1]"""
+        x, px = _u64(np.asarray(inputs).reshape(-1))
+        n = x.size // (12 * self.num_inputs) if self.num_inputs else int(np.asarray(inputs).shape[0])
+        out = np.zeros((n, 24), dtype=np.uint64)
+        _check(lib().mnt753_vk_accumulate(self._h, px, n, out.ctypes.data_as(C.POINTER(C.c_uint64))), "mnt753_vk_accumulate")
+        return out
+
+    def verify(self, proofs, inputs, on_device=False, n=None, stream=None):
+        """proofs: n x (A | B | C) affine wire words, inputs: n x num_inputs Fr (numpy arrays, or device addresses with on_device and n)
+        -> numpy uint8 verdicts [n]: 0 accepted, 1 malformed, 2 the pairing check failed"""
+        pw = 48 + affine_words(self.curve, G2)
+        pp, cnt, keep1 = _input_ptr(proofs, on_device, pw, n)
+        if self.num_inputs:
+            pi, cnt2, keep2 = _input_ptr(inputs, on_device, 12 * self.num_inputs, n)
+            if cnt2 != cnt:
+                raise Mnt753Error("verify: one row of inputs per proof")
+        else:
+            pi = C.c_void_p()
+        verdicts = np.zeros(cnt, dtype=np.uint8)
+        st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+        rc = lib().mnt753_groth16_verify(self._h, pp, pi, cnt, 1 if on_device else 0, C.c_void_p(verdicts.ctypes.data), st)
+        if rc < 0:
+            _check(rc, "mnt753_groth16_verify")
+        return verdicts
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().mnt753_vk_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def test_tower_op(curve, split, op, a, b=None):
+    """mnt753_test_tower_op (test library): a, b [n, gt_words] -> [n, gt_words]"""
+    a, pa = _u64(a)
+    b, pb = _u64(a if b is None else b)
+    out = np.zeros_like(a)
+    n = a.size // gt_words(curve)
+    _check(test_lib().mnt753_test_tower_op(curve, split, op, pa, pb, n, out.ctypes.data_as(C.POINTER(C.c_uint64))), "mnt753_test_tower_op")
+    return out.reshape(n, -1)
+
+
+def test_miller_loop(curve, split, P, Q):
+    """mnt753_test_miller_loop (test library): the unreduced Miller values [n, gt_words]"""
+    p, pp = _u64(P)
+    q, pq = _u64(Q)
+    n = p.size // 24
+    out = np.zeros((n, gt_words(curve)), dtype=np.uint64)
+    _check(test_lib().mnt753_test_miller_loop(curve, split, pp, pq, n, out.ctypes.data_as(C.POINTER(C.c_uint64))), "mnt753_test_miller_loop")
+    return out

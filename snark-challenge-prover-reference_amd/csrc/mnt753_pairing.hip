@@ -1,0 +1,325 @@
+// C ABI of the pairing and of Groth16 verification: mnt753_gt_words, mnt753_pairing, mnt753_vk_*, mnt753_groth16_verify
+// (include/mnt753_hip.h).  Kernels: pairing_kernels.hip.h.
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+#include "common_host.hpp"
+#include "mnt753_generators.h"
+#include "pairing_kernels.hip.h"
+
+namespace mnt753 {
+namespace {
+
+// device memory of one call
+struct PairingBuffers {
+  void *g1 = nullptr, *g2 = nullptr, *out = nullptr, *stand = nullptr, *ints = nullptr;
+  ~PairingBuffers() {
+    for (void* p : {g1, g2, out, stand, ints})
+      if (p) (void)hipFree(p);
+  }
+};
+
+int alloc(void** p, size_t bytes) {
+  if (hipMalloc(p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    *p = nullptr;
+    return set_error(MNT753_ENOMEM, "pairing: device allocation failed");
+  }
+  return 0;
+}
+
+bool y_is_zero(const uint64_t* pt, size_t words) {
+  for (size_t k = words / 2; k < words; ++k)
+    if (pt[k]) return false;
+  return true;
+}
+
+constexpr size_t VERIFY_CHUNK = (size_t)1 << 16;   // proofs per launch: bounds the workspace of a batch
+
+constexpr size_t MAX_PAIRINGS = (size_t)1 << 24;   // logical lanes are 32-bit, and the grid is n / 128 (n / 84) workgroups
+
+}  // namespace
+}  // namespace mnt753
+
+// a verification key: libsnark's r1cs_gg_ppzksnark_processed_verification_key, the coefficients of its two G2 points on the device
+struct mnt753_vk {
+  int curve = 0, device = 0;
+  size_t num_inputs = 0;
+  std::vector<uint64_t> delta, abc, gt;
+  uint64_t* dev_key = nullptr;   // stand-in G1 (the generator) | G2::one() | delta_g2 | e(alpha, beta)
+  uint64_t* dev_abc = nullptr;   // num_inputs + 1 G1 points
+  uint32_t* dev_coeffs = nullptr;   // the Miller-loop coefficients of G2::one(), then of delta_g2 (k_g2_precompute)
+  size_t workspace_cap = 0;      // bytes a verify call may allocate; 0: the default chunk of 2^16 proofs
+};
+
+using namespace mnt753;
+
+extern "C" {
+
+size_t mnt753_gt_words(int curve) { return curve == MNT753_CURVE_MNT4753 ? 48 : (curve == MNT753_CURVE_MNT6753 ? 72 : 0); }
+
+int mnt753_pairing(int curve, const uint64_t* g1_affine, const uint64_t* g2_affine, size_t n, int on_device, uint64_t* out_gt, void* stream) {
+  if (curve < 0 || curve > 1 || (n && (!g1_affine || !g2_affine || !out_gt)) || n > MAX_PAIRINGS) return set_error(MNT753_EINVAL, "pairing: bad argument");
+  if (int rc = require_device()) return rc;
+  if (!n) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t w2 = mnt753_affine_words(curve, MNT753_G2), wt = mnt753_gt_words(curve);
+  PairingBuffers buf;
+  uint64_t* dev_out = out_gt;
+  if (!on_device) {
+    if (int rc = alloc(&buf.g1, 8 * 24 * n)) return rc;
+    if (int rc = alloc(&buf.g2, 8 * w2 * n)) return rc;
+    if (int rc = alloc(&buf.out, 8 * wt * n)) return rc;
+    HIP_TRY(hipMemcpyAsync(buf.g1, g1_affine, 8 * 24 * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(buf.g2, g2_affine, 8 * w2 * n, hipMemcpyHostToDevice, st));
+    g1_affine = reinterpret_cast<const uint64_t*>(buf.g1);
+    g2_affine = reinterpret_cast<const uint64_t*>(buf.g2);
+    dev_out = reinterpret_cast<uint64_t*>(buf.out);
+  }
+  // is_well_formed() of both arguments: a malformed point is an error of the call, nothing is computed
+  for (int group = MNT753_G1; group <= MNT753_G2; ++group) {
+    mnt753_check_report rep;
+    if (int rc = mnt753_check_points(curve, group, group == MNT753_G1 ? g1_affine : g2_affine, 1, n, &rep, stream)) return rc;
+    if (rep.n_bad) return set_error(MNT753_EINPUT, group == MNT753_G1 ? "pairing: a G1 point is non-canonical or off the curve"
+                                                                       : "pairing: a G2 point is non-canonical or off the curve");
+  }
+  // the stand-in pair of a lane group whose argument is the identity: the generators
+  if (int rc = alloc(&buf.stand, 8 * (24 + w2))) return rc;
+  HIP_TRY(hipMemcpyAsync(buf.stand, curve == MNT753_CURVE_MNT4753 ? GEN_MNT4_G1 : GEN_MNT6_G1, 8 * 24, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(reinterpret_cast<uint64_t*>(buf.stand) + 24, curve == MNT753_CURVE_MNT4753 ? GEN_MNT4_G2 : GEN_MNT6_G2, 8 * w2,
+                         hipMemcpyHostToDevice, st));
+  const uint32_t* s1 = reinterpret_cast<const uint32_t*>(buf.stand);
+  const uint32_t* s2 = s1 + 48;
+  const uint32_t *p1 = reinterpret_cast<const uint32_t*>(g1_affine), *p2 = reinterpret_cast<const uint32_t*>(g2_affine);
+  uint32_t* po = reinterpret_cast<uint32_t*>(dev_out);
+  if (curve == MNT753_CURVE_MNT4753)
+    hipLaunchKernelGGL((k_pairing<Mnt4G2S>), dim3(blocks_for<Mnt4G2S::F>(n)), dim3(256), 0, st, p1, p2, s1, s2, po, (uint32_t)n, 0);
+  else
+    hipLaunchKernelGGL((k_pairing<Mnt6G2S>), dim3(blocks_for<Mnt6G2S::F>(n)), dim3(256), 0, st, p1, p2, s1, s2, po, (uint32_t)n, 0);
+  HIP_TRY(hipGetLastError());
+  if (!on_device) HIP_TRY(hipMemcpyAsync(out_gt, dev_out, 8 * wt * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));             // the call's buffers go when it returns
+  return 0;
+}
+
+int mnt753_vk_create(int curve, const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* delta_g2, const uint64_t* abc_g1, size_t num_inputs,
+                     mnt753_vk** out) {
+  if (curve < 0 || curve > 1 || !alpha_g1 || !beta_g2 || !delta_g2 || !abc_g1 || !out || num_inputs > ((size_t)1 << 20))
+    return set_error(MNT753_EINVAL, "vk_create: bad argument");
+  if (int rc = require_device()) return rc;
+  const size_t w2 = mnt753_affine_words(curve, MNT753_G2), wt = mnt753_gt_words(curve);
+  // every element of a key is a point of its curve other than the identity
+  struct { const uint64_t* p; int group; size_t n; } parts[4] = {{alpha_g1, MNT753_G1, 1}, {beta_g2, MNT753_G2, 1}, {delta_g2, MNT753_G2, 1},
+                                                                {abc_g1, MNT753_G1, num_inputs + 1}};
+  for (const auto& part : parts) {
+    const size_t w = part.group == MNT753_G1 ? 24 : w2;
+    for (size_t k = 0; k < part.n; ++k)
+      if (y_is_zero(part.p + k * w, w)) return set_error(MNT753_EINVAL, "vk_create: an element of the key is the identity");
+    mnt753_check_report rep;
+    if (int rc = mnt753_check_points(curve, part.group, part.p, 0, part.n, &rep, nullptr)) return rc;
+    if (rep.n_bad) return set_error(MNT753_EINPUT, "vk_create: an element of the key is non-canonical or off its curve");
+  }
+  mnt753_vk* vk = new mnt753_vk;
+  vk->curve = curve;
+  vk->device = current_physical_device();
+  vk->num_inputs = num_inputs;
+  vk->delta.assign(delta_g2, delta_g2 + w2);
+  vk->abc.assign(abc_g1, abc_g1 + 24 * (num_inputs + 1));
+  vk->gt.resize(wt);
+  int rc = mnt753_pairing(curve, alpha_g1, beta_g2, 1, 0, vk->gt.data(), nullptr);
+  if (!rc) {
+    std::vector<uint64_t> key(24 + 2 * w2 + wt);
+    memcpy(key.data(), curve == MNT753_CURVE_MNT4753 ? GEN_MNT4_G1 : GEN_MNT6_G1, 8 * 24);
+    memcpy(key.data() + 24, curve == MNT753_CURVE_MNT4753 ? GEN_MNT4_G2 : GEN_MNT6_G2, 8 * w2);
+    memcpy(key.data() + 24 + w2, delta_g2, 8 * w2);
+    memcpy(key.data() + 24 + 2 * w2, vk->gt.data(), 8 * wt);
+    if (hipMalloc(&vk->dev_key, 8 * key.size()) != hipSuccess || hipMalloc(&vk->dev_abc, 8 * vk->abc.size()) != hipSuccess) {
+      (void)hipGetLastError();
+      rc = set_error(MNT753_ENOMEM, "vk_create: device allocation failed");
+    } else if (hipMemcpy(vk->dev_key, key.data(), 8 * key.size(), hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(vk->dev_abc, vk->abc.data(), 8 * vk->abc.size(), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      rc = set_error(MNT753_EHIP, "vk_create: copy to the device failed");
+    } else {
+      // ate_precompute_G2 of G2::one() and delta_g2, once: one lane group each, into the key object
+      const size_t cw = curve == MNT753_CURVE_MNT4753 ? ate_coeff_words<Mnt4G2S>() : ate_coeff_words<Mnt6G2S>();
+      if (hipMalloc(&vk->dev_coeffs, 4 * 2 * cw) != hipSuccess) {
+        (void)hipGetLastError();
+        rc = set_error(MNT753_ENOMEM, "vk_create: device allocation failed");
+      } else {
+        const uint32_t* k32 = reinterpret_cast<const uint32_t*>(vk->dev_key);
+        for (int which = 0; which < 2; ++which) {
+          const uint32_t* q = k32 + 48 + which * 2 * w2;          // G2::one(), then delta_g2
+          if (curve == MNT753_CURVE_MNT4753) hipLaunchKernelGGL((k_g2_precompute<Mnt4G2S>), dim3(1), dim3(256), 0, 0, q, vk->dev_coeffs + which * cw);
+          else hipLaunchKernelGGL((k_g2_precompute<Mnt6G2S>), dim3(1), dim3(256), 0, 0, q, vk->dev_coeffs + which * cw);
+        }
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+          (void)hipGetLastError();
+          rc = set_error(MNT753_EHIP, "vk_create: the precomputation of the key's G2 points failed");
+        }
+      }
+    }
+  }
+  if (rc) { mnt753_vk_destroy(vk); return rc; }
+  *out = vk;
+  return 0;
+}
+
+int mnt753_vk_destroy(mnt753_vk* vk) {
+  if (!vk) return 0;
+  OnDevice guard(vk->device);
+  if (vk->dev_key) (void)hipFree(vk->dev_key);
+  if (vk->dev_abc) (void)hipFree(vk->dev_abc);
+  if (vk->dev_coeffs) (void)hipFree(vk->dev_coeffs);
+  delete vk;
+  return 0;
+}
+
+size_t mnt753_vk_num_inputs(const mnt753_vk* vk) { return vk ? vk->num_inputs : 0; }
+
+size_t mnt753_vk_coefficient_bytes(const mnt753_vk* vk) {
+  if (!vk) return 0;
+  return 4 * 2 * (size_t)(vk->curve == MNT753_CURVE_MNT4753 ? ate_coeff_words<Mnt4G2S>() : ate_coeff_words<Mnt6G2S>());
+}
+
+int mnt753_vk_set_workspace_cap(mnt753_vk* vk, size_t bytes) {
+  if (!vk) return set_error(MNT753_EINVAL, "vk_set_workspace_cap: bad argument");
+  vk->workspace_cap = bytes;
+  return 0;
+}
+
+int mnt753_vk_gt(const mnt753_vk* vk, uint64_t* out) {
+  if (!vk || !out) return set_error(MNT753_EINVAL, "vk_gt: bad argument");
+  memcpy(out, vk->gt.data(), 8 * vk->gt.size());
+  return 0;
+}
+
+int mnt753_vk_serialize(const mnt753_vk* vk, uint8_t* buf, size_t cap, size_t* len) {
+  if (!vk || !len) return set_error(MNT753_EINVAL, "vk_serialize: bad argument");
+  std::vector<uint8_t> o;
+  auto raw = [&](const uint64_t* p, size_t words) { o.insert(o.end(), (const uint8_t*)p, (const uint8_t*)p + 8 * words); };
+  auto num = [&](size_t v) { char t[32]; const int k = snprintf(t, sizeof(t), "%zu\n", v); o.insert(o.end(), t, t + k); };
+  // operator<< of r1cs_gg_ppzksnark_verification_key: alpha_g1_beta_g2, delta_g2, ABC_g1 (an accumulation_vector: first, then the
+  // sparse_vector of the rest); a point under NO_PT_COMPRESSION is the byte '0' (not the identity) and X | Y
+  raw(vk->gt.data(), vk->gt.size());
+  o.push_back('0'); raw(vk->delta.data(), vk->delta.size());
+  o.push_back('0'); raw(vk->abc.data(), 24);
+  const size_t n = vk->num_inputs;
+  num(n); num(n);
+  for (size_t i = 0; i < n; ++i) num(i);
+  num(n);
+  for (size_t j = 1; j <= n; ++j) { o.push_back('0'); raw(vk->abc.data() + 24 * j, 24); }
+  *len = o.size();
+  if (!buf) return 0;                            // the size only
+  if (cap < o.size()) return set_error(MNT753_EINVAL, "vk_serialize: buffer too small");
+  memcpy(buf, o.data(), o.size());
+  return 0;
+}
+
+namespace {
+// inputs (device, n x num_inputs Fr) -> dev_acc (n G1 points, affine wire form), dev_bad[t] = 1 where an input is >= r.  ints: room for
+// the inputs as integers, 96 num_inputs n bytes (unused without inputs).  Enqueues only.
+int accumulate_on_device(const mnt753_vk* vk, const uint64_t* dev_inputs, size_t n, uint64_t* dev_acc, uint8_t* dev_bad, uint32_t* ints, hipStream_t st) {
+  const size_t ni = vk->num_inputs;
+  if (!ni) HIP_TRY(hipMemsetAsync(dev_bad, 0, n, st));
+  const dim3 g((unsigned)((n + 255) / 256)), b(256);
+  const uint32_t* in = reinterpret_cast<const uint32_t*>(dev_inputs);
+  const uint32_t* abc = reinterpret_cast<const uint32_t*>(vk->dev_abc);
+  uint32_t* out = reinterpret_cast<uint32_t*>(dev_acc);
+  if (vk->curve == MNT753_CURVE_MNT4753) {
+    if (ni) hipLaunchKernelGGL((k_inputs_to_integer<MOD_A>), g, b, 0, st, in, ints, dev_bad, (uint32_t)n, (uint32_t)ni);
+    hipLaunchKernelGGL((k_vk_accumulate<Mnt4G1>), g, b, 0, st, abc, ints, out, (uint32_t)n, (uint32_t)ni);
+  } else {
+    if (ni) hipLaunchKernelGGL((k_inputs_to_integer<MOD_B>), g, b, 0, st, in, ints, dev_bad, (uint32_t)n, (uint32_t)ni);
+    hipLaunchKernelGGL((k_vk_accumulate<Mnt6G1>), g, b, 0, st, abc, ints, out, (uint32_t)n, (uint32_t)ni);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+// a device pointer of the caller lies on the key's device
+bool on_device_of(const void* p, int device) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return a.device == device;
+}
+}  // namespace
+
+int mnt753_vk_accumulate(const mnt753_vk* vk, const uint64_t* inputs, size_t n, uint64_t* out_affine) {
+  if (!vk || (n && (!out_affine || (vk->num_inputs && !inputs))) || n > MAX_PAIRINGS) return set_error(MNT753_EINVAL, "vk_accumulate: bad argument");
+  if (int rc = require_device()) return rc;
+  if (!n) return 0;
+  OnDevice guard(vk->device);
+  PairingBuffers buf;   // g1: the inputs, out: the points, g2: the flags
+  const size_t ni = vk->num_inputs;
+  if (ni) {
+    if (int rc = alloc(&buf.g1, 96 * ni * n)) return rc;
+    if (int rc = alloc(&buf.ints, 96 * ni * n)) return rc;
+    HIP_TRY(hipMemcpy(buf.g1, inputs, 96 * ni * n, hipMemcpyHostToDevice));
+  }
+  if (int rc = alloc(&buf.out, 192 * n)) return rc;
+  if (int rc = alloc(&buf.g2, n)) return rc;
+  if (int rc = accumulate_on_device(vk, reinterpret_cast<const uint64_t*>(buf.g1), n, reinterpret_cast<uint64_t*>(buf.out),
+                                    reinterpret_cast<uint8_t*>(buf.g2), reinterpret_cast<uint32_t*>(buf.ints), nullptr)) return rc;
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  std::vector<uint8_t> bad(n);
+  HIP_TRY(hipMemcpy(bad.data(), buf.g2, n, hipMemcpyDeviceToHost));
+  for (uint8_t b : bad)
+    if (b) return set_error(MNT753_EINPUT, "vk_accumulate: an input is not below r");
+  HIP_TRY(hipMemcpy(out_affine, buf.out, 192 * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int mnt753_groth16_verify(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int on_device, uint8_t* verdicts, void* stream) {
+  if (!vk || (n && (!proofs || !verdicts || (vk->num_inputs && !inputs))) || n > MAX_PAIRINGS) return set_error(MNT753_EINVAL, "groth16_verify: bad argument");
+  if (int rc = require_device()) return rc;
+  if (!n) return 0;
+  OnDevice guard(vk->device);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t ni = vk->num_inputs, w2 = mnt753_affine_words(vk->curve, MNT753_G2), pw = 48 + w2;   // words of one proof
+  if (on_device && (!on_device_of(proofs, vk->device) || (ni && !on_device_of(inputs, vk->device))))
+    return set_error(MNT753_EINVAL, "groth16_verify: proofs and inputs must lie on the device of the key");
+  // what one proof of a chunk takes: the accumulated point, the inputs as integers, flag and verdict, and its staged copy if it
+  // arrives in host memory.  The cap of the key bounds the chunk (at least one proof, at most 2^16).
+  const size_t per_proof = 194 + 96 * ni + (on_device ? 0 : 8 * pw + 96 * ni);
+  size_t chunk = n < VERIFY_CHUNK ? n : VERIFY_CHUNK;
+  if (vk->workspace_cap && vk->workspace_cap / per_proof < chunk) chunk = vk->workspace_cap / per_proof ? vk->workspace_cap / per_proof : 1;
+  PairingBuffers buf;   // g1: staged proofs, g2: staged inputs, out: accumulated points, stand: flags then verdicts, ints: inputs as integers
+  if (!on_device) {
+    if (int rc = alloc(&buf.g1, 8 * pw * chunk)) return rc;
+    if (ni) { if (int rc = alloc(&buf.g2, 96 * ni * chunk)) return rc; }
+  }
+  if (ni) { if (int rc = alloc(&buf.ints, 96 * ni * chunk)) return rc; }
+  if (int rc = alloc(&buf.out, 192 * chunk)) return rc;
+  if (int rc = alloc(&buf.stand, 2 * chunk)) return rc;
+  uint8_t* dev_bad = reinterpret_cast<uint8_t*>(buf.stand);
+  uint8_t* dev_verdicts = dev_bad + chunk;
+  size_t rejected = 0;
+  for (size_t first = 0; first < n; first += chunk) {
+    const size_t cnt = n - first < chunk ? n - first : chunk;
+    const uint64_t* dp = proofs + first * pw;
+    const uint64_t* di = ni ? inputs + first * ni * 12 : nullptr;
+    if (!on_device) {
+      HIP_TRY(hipMemcpyAsync(buf.g1, dp, 8 * pw * cnt, hipMemcpyHostToDevice, st));
+      dp = reinterpret_cast<const uint64_t*>(buf.g1);
+      if (ni) {
+        HIP_TRY(hipMemcpyAsync(buf.g2, di, 96 * ni * cnt, hipMemcpyHostToDevice, st));
+        di = reinterpret_cast<const uint64_t*>(buf.g2);
+      }
+    }
+    if (int rc = accumulate_on_device(vk, di, cnt, reinterpret_cast<uint64_t*>(buf.out), dev_bad, reinterpret_cast<uint32_t*>(buf.ints), st)) return rc;
+    const uint32_t *p = reinterpret_cast<const uint32_t*>(dp), *acc = reinterpret_cast<const uint32_t*>(buf.out),
+                   *key = reinterpret_cast<const uint32_t*>(vk->dev_key);
+    if (vk->curve == MNT753_CURVE_MNT4753)
+      hipLaunchKernelGGL((k_groth16_verify<Mnt4G2S, Mnt4G1>), dim3(blocks_for<Mnt4G2S::F>(cnt)), dim3(256), 0, st, p, acc, key, vk->dev_coeffs, dev_bad, dev_verdicts, (uint32_t)cnt);
+    else
+      hipLaunchKernelGGL((k_groth16_verify<Mnt6G2S, Mnt6G1>), dim3(blocks_for<Mnt6G2S::F>(cnt)), dim3(256), 0, st, p, acc, key, vk->dev_coeffs, dev_bad, dev_verdicts, (uint32_t)cnt);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(verdicts + first, dev_verdicts, cnt, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t k = 0; k < cnt; ++k) rejected += verdicts[first + k] != 0;
+  }
+  return (int)rejected;
+}
+
+}  // extern "C"

@@ -1,0 +1,94 @@
+// TEST INFRASTRUCTURE (libmnt753_hip_test.so, include/mnt753_hip_test.h) -- not linked into the product library.
+// The tower of tower753.hip.h and the two halves of the pairing (pairing_kernels.hip.h) exposed element-wise, in the one-lane and in
+// the lane-split form, so that tests/test_pairing_gpu.py can pin them against the Python-integer model (tests/pairing_ref.py): an
+// error in the Miller loop that the final exponentiation happens to map to the right GT element still shows in the unreduced value.
+#include <hip/hip_runtime.h>
+
+#include "common_host.hpp"
+#include "../../include/mnt753_hip_test.h"
+#include "pairing_kernels.hip.h"
+
+using namespace mnt753;
+
+namespace {
+struct DevBuf {   // freed on every path out of a hook
+  uint32_t* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+// op: 0 a b, 1 a^2, 2 a^-1 (0 -> 0), 3 the unitary inverse, 4 a^|w0|, 5 the final exponentiation of a, 10 + i: a^(q^i)
+template <class C>
+__global__ void __launch_bounds__(256, 1) k_tower_op(int op, const uint32_t* __restrict__ a_wire, const uint32_t* __restrict__ b_wire,
+                                                    uint32_t* __restrict__ out_wire, uint32_t n) {
+  using F = typename C::F;
+  using T = Tower<F>;
+  constexpr int HW = 24 * F::DEG;   // wire words of one half
+  const uint32_t t = logical_lane<F>();
+  if (t == 0xffffffffu || t >= n) return;
+  typename T::E a, b, r;
+  wire_load<F>(a.c0, a_wire + (size_t)t * 2 * HW); wire_load<F>(a.c1, a_wire + (size_t)t * 2 * HW + HW);
+  wire_load<F>(b.c0, b_wire + (size_t)t * 2 * HW); wire_load<F>(b.c1, b_wire + (size_t)t * 2 * HW + HW);
+  switch (op) {
+    case 0: T::mul(r, a, b); break;
+    case 1: T::sqr(r, a); break;
+    case 2: T::inv(r, a); break;
+    case 3: T::unitary_inverse(r, a); break;
+    case 4: T::pow(r, a, PAIRC[Ate<C>::CURVE].w0_abs, PAIRC[Ate<C>::CURVE].w0_bits); break;
+    case 5: Ate<C>::final_exponentiation(r, a); break;
+    case 11: T::template frobenius<1>(r, a); break;
+    case 12: T::template frobenius<2>(r, a); break;
+    case 13: T::template frobenius<3>(r, a); break;
+    case 14: T::template frobenius<4>(r, a); break;
+    default: T::template frobenius<5>(r, a); break;
+  }
+  wire_store<F>(out_wire + (size_t)t * 2 * HW, r.c0);
+  wire_store<F>(out_wire + (size_t)t * 2 * HW + HW, r.c1);
+}
+
+template <class C>
+int run_tower_op(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
+  using F = typename C::F;
+  const size_t bytes = 8 * 24 * (size_t)F::DEG * n;
+  DevBuf da, db, dout;
+  HIP_TRY(hipMalloc(&da.p, bytes)); HIP_TRY(hipMalloc(&db.p, bytes)); HIP_TRY(hipMalloc(&dout.p, bytes));
+  HIP_TRY(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL((k_tower_op<C>), dim3(blocks_for<F>(n)), dim3(256), 0, 0, op, da.p, db.p, dout.p, (uint32_t)n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// the unreduced Miller value of n pairs (neither argument the identity)
+template <class C>
+int run_miller(const uint64_t* g1, const uint64_t* g2, size_t n, uint64_t* out) {
+  using F = typename C::F;
+  const size_t b1 = 8 * 24 * n, b2 = 8 * 24 * (size_t)F::DEG * n;
+  DevBuf d1, d2, dout;
+  HIP_TRY(hipMalloc(&d1.p, b1)); HIP_TRY(hipMalloc(&d2.p, b2)); HIP_TRY(hipMalloc(&dout.p, b2));
+  HIP_TRY(hipMemcpy(d1.p, g1, b1, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d2.p, g2, b2, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL((k_pairing<C>), dim3(blocks_for<F>(n)), dim3(256), 0, 0, d1.p, d2.p, d1.p, d2.p, dout.p, (uint32_t)n, 1);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout.p, b2, hipMemcpyDeviceToHost));
+  return 0;
+}
+}  // namespace
+
+extern "C" int mnt753_test_tower_op(int curve, int split, int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
+  const int k = curve == MNT753_CURVE_MNT4753 ? 4 : 6;
+  if (curve < 0 || curve > 1 || !((op >= 0 && op <= 5) || (op >= 11 && op < 10 + k)) || (n && (!a || !b || !out)) || n > 0xffffffu)
+    return set_error(MNT753_EINVAL, "test_tower_op: bad argument");
+  if (int rc = require_device()) return rc;
+  if (n == 0) return 0;
+  if (curve == MNT753_CURVE_MNT4753) return split ? run_tower_op<Mnt4G2S>(op, a, b, n, out) : run_tower_op<Mnt4G2>(op, a, b, n, out);
+  return split ? run_tower_op<Mnt6G2S>(op, a, b, n, out) : run_tower_op<Mnt6G2>(op, a, b, n, out);
+}
+
+extern "C" int mnt753_test_miller_loop(int curve, int split, const uint64_t* g1_affine, const uint64_t* g2_affine, size_t n, uint64_t* out) {
+  if (curve < 0 || curve > 1 || (n && (!g1_affine || !g2_affine || !out)) || n > 0xffffffu) return set_error(MNT753_EINVAL, "test_miller_loop: bad argument");
+  if (int rc = require_device()) return rc;
+  if (n == 0) return 0;
+  if (curve == MNT753_CURVE_MNT4753) return split ? run_miller<Mnt4G2S>(g1_affine, g2_affine, n, out) : run_miller<Mnt4G2>(g1_affine, g2_affine, n, out);
+  return split ? run_miller<Mnt6G2S>(g1_affine, g2_affine, n, out) : run_miller<Mnt6G2>(g1_affine, g2_affine, n, out);
+}

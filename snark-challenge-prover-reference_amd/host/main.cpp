@@ -29,6 +29,7 @@
 
 #include "../../include/mnt753_hip.h"
 #include "../../include/prover_hip_functions.hpp"
+#include "../csrc/mnt753_constants.h"   // FPC[].one64: the wire form of 1
 
 // Defaults = the fastest schedule on one MI355X: the G2 MSM is enqueued as soon as w is on the device, compute_H (one fused
 // call) follows as soon as ca / cb / cc are, then the G1 MSMs.  The point kernels occupy every SIMD with long-lived
@@ -591,8 +592,96 @@ static int generate_key(int curve, const char* r1cs_path, const char* out_dir, c
   return 0;
 }
 
+// `main_hip <curve> vk <vk_elements.bin> <out>` writes the complete verification key (the reference's vk.txt: mnt753_vk_serialize);
+// `main_hip <curve> verify <vk_elements.bin> <input_or_witness> <proof> [<proof> ...]` prints VERIFIED or REJECTED per proof
+// (B::verify = mnt753_vk_create + mnt753_groth16_verify) and exits 0 if all are accepted, 3 otherwise.  vk_elements.bin: alpha_g1 | beta_g2 | delta_g2 | ABC_g1, so
+// its size gives num_inputs; the input (or witness) file starts with 1 and the num_inputs public inputs.
+static bool read_all_words(const char* path, std::vector<uint64_t>& out) {
+  FILE* f = fopen(path, "rb");
+  if (!f) { fprintf(stderr, "main_hip: cannot read %s\n", path); return false; }
+  uint64_t buf[4096];
+  size_t got;
+  out.clear();
+  while ((got = fread(buf, 1, sizeof(buf), f)) > 0) {
+    if (got % 8) { fclose(f); fprintf(stderr, "main_hip: %s is not a whole number of words\n", path); return false; }
+    out.insert(out.end(), buf, buf + got / 8);
+  }
+  fclose(f);
+  return true;
+}
+static int vk_command(int curve, bool verify, const std::vector<const char*>& pos) {
+  const size_t w2 = mnt753_affine_words(curve, MNT753_G2);
+  std::vector<uint64_t> el;
+  if (!read_all_words(pos[0], el)) return 1;
+  if (el.size() < 48 + 2 * w2 || (el.size() - 24 - 2 * w2) % 24) { fprintf(stderr, "main_hip: %s does not hold alpha_g1 | beta_g2 | delta_g2 | ABC_g1\n", pos[0]); return 3; }
+  const size_t num_inputs = (el.size() - 24 - 2 * w2) / 24 - 1;
+  std::vector<uint64_t> inputs, proofs;
+  if (verify) {
+    FILE* f = fopen(pos[1], "rb");
+    inputs.resize(12 * (num_inputs + 1));
+    const bool ok = f && fread(inputs.data(), 8, inputs.size(), f) == inputs.size();
+    if (f) fclose(f);
+    if (!ok) { fprintf(stderr, "main_hip: cannot read 1 + %zu elements from %s\n", num_inputs, pos[1]); return 1; }
+    // the leading element is the constant 1: R mod r, the Montgomery one of Fr (modulus A on MNT4753, B on MNT6753)
+    if (memcmp(inputs.data(), mnt753::FPC[curve].one64, 96) != 0) { fprintf(stderr, "main_hip: %s does not start with the constant 1\n", pos[1]); return 3; }
+    for (size_t k = 2; k < pos.size(); ++k) {
+      std::vector<uint64_t> one;
+      if (!read_all_words(pos[k], one)) return 1;
+      if (one.size() != 48 + w2) { fprintf(stderr, "main_hip: %s is not a proof A | B | C\n", pos[k]); return 3; }
+      proofs.insert(proofs.end(), one.begin(), one.end());
+    }
+  }
+  if (mnt753_init(0) != 0) { fprintf(stderr, "main_hip: %s\n", mnt753_last_error()); return 1; }
+  if (verify) {
+    // through the wrapper class, as a C++ caller would: B::verify makes the key, verifies the batch and drops the key
+    const size_t n = pos.size() - 2;
+    std::vector<uint64_t> per_proof;
+    for (size_t k = 0; k < n; ++k) per_proof.insert(per_proof.end(), inputs.begin() + 12, inputs.end());
+    std::vector<uint8_t> verdicts;
+    try {
+      verdicts = curve == 0 ? mnt4753_hip::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n)
+                            : mnt6753_hip::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n);
+    } catch (const std::exception& e) { fprintf(stderr, "main_hip: %s\n", e.what()); return 1; }
+    int bad = 0;
+    for (size_t k = 0; k < n; ++k) { printf("%s\n", verdicts[k] == 0 ? "VERIFIED" : "REJECTED"); bad += verdicts[k] != 0; }
+    return bad ? 3 : 0;
+  }
+  mnt753_vk* vk = nullptr;
+  const int rc = mnt753_vk_create(curve, el.data(), el.data() + 24, el.data() + 24 + w2, el.data() + 24 + 2 * w2, num_inputs, &vk);
+  if (rc != 0) { fprintf(stderr, "main_hip: %s\n", mnt753_last_error()); return rc == MNT753_EINPUT || rc == MNT753_EINVAL ? 3 : 1; }
+  int ret = 0;
+  size_t len = 0;
+  mnt753_vk_serialize(vk, nullptr, 0, &len);
+  std::vector<uint8_t> bytes(len);
+  if (mnt753_vk_serialize(vk, bytes.data(), len, &len) != 0) { fprintf(stderr, "main_hip: %s\n", mnt753_last_error()); ret = 1; }
+  else {
+    FILE* o = fopen(pos[1], "wb");
+    const bool wrote = o && fwrite(bytes.data(), 1, len, o) == len;
+    if (!o || fclose(o) != 0 || !wrote) { fprintf(stderr, "main_hip: cannot write %s\n", pos[1]); ret = 1; }
+  }
+  mnt753_vk_destroy(vk);
+  return ret;
+}
+
 int main(int argc, char** argv) {
   setbuf(stdout, NULL);
+  if (argc >= 3 && (!strcmp(argv[2], "vk") || !strcmp(argv[2], "verify"))) {
+    const bool verify = !strcmp(argv[2], "verify");
+    const int curve = !strcmp(argv[1], "MNT4753") ? 0 : (!strcmp(argv[1], "MNT6753") ? 1 : -1);
+    if (curve < 0) { fprintf(stderr, "unknown curve %s\n", argv[1]); return 2; }
+    std::vector<const char*> pos;
+    for (int i = 3; i < argc; ++i) {
+      if (argv[i][0] == '-') { fprintf(stderr, "main_hip: unknown option %s\n", argv[i]); return 2; }
+      pos.push_back(argv[i]);
+    }
+    if (verify ? pos.size() < 3 : pos.size() != 2) {
+      fprintf(stderr, "usage: %s MNT4753|MNT6753 vk <vk_elements.bin> <out>\n       %s MNT4753|MNT6753 verify <vk_elements.bin> <input_or_witness> <proof> [<proof> ...]\n"
+                      "  vk: writes the complete verification key (with the GT element e(alpha_g1, beta_g2)) in the reference's vk.txt format.\n"
+                      "  verify: prints VERIFIED or REJECTED per proof; exit code 0 if every proof is accepted, 3 otherwise.\n", argv[0], argv[0]);
+      return 2;
+    }
+    return vk_command(curve, verify, pos);
+  }
   if (argc >= 3 && !strcmp(argv[2], "generate")) {
     const int curve = !strcmp(argv[1], "MNT4753") ? 0 : (!strcmp(argv[1], "MNT6753") ? 1 : -1);
     if (curve < 0) { fprintf(stderr, "unknown curve %s\n", argv[1]); return 2; }
@@ -610,7 +699,8 @@ int main(int argc, char** argv) {
     if (pos.size() != 2) {
       fprintf(stderr, "usage: %s MNT4753|MNT6753 generate <r1cs> <out_dir> [--randomness <file>] [--mixed-radix] [--quiet]\n"
                       "  writes params.bin, keys.bin, vk_elements.bin (alpha_g1 | beta_g2 | delta_g2 | ABC_g1) and r1cs.bin into <out_dir>.\n"
-                      "  The GT element alpha_g1_beta_g2 of a libsnark verification key needs a pairing and is left to the verifying side.\n"
+                      "  The GT element alpha_g1_beta_g2 of a libsnark verification key is a pairing of two of these: `vk <vk_elements.bin> <out>`\n"
+                      "  writes the complete key, `verify` checks proofs against it.\n"
                       "  <file>: t | alpha | beta | delta (4 x 96 bytes) and the G1 generator (affine); without it the scalars are drawn from the\n"
                       "  operating system's generator and written nowhere, and the G1 generator is the curve's standard one.\n", argv[0]);
       return 2;

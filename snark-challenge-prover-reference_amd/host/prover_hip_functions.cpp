@@ -1380,5 +1380,21 @@ template <int CURVE> typename HIP_B::check_report HIP_B::check_witness_file(cons
   return rep;
 }
 
+template <int CURVE> std::vector<uint64_t> HIP_B::pairing(const uint64_t* g1_affine, const uint64_t* g2_affine, size_t n) {
+  std::vector<uint64_t> out(n * mnt753_gt_words(CURVE));
+  check(mnt753_pairing(CURVE, g1_affine, g2_affine, n, 0, out.data(), nullptr), "mnt753_pairing");
+  return out;
+}
+template <int CURVE> std::vector<uint8_t> HIP_B::verify(const uint64_t* vk_elements, size_t num_inputs, const uint64_t* proofs, const uint64_t* inputs, size_t n) {
+  const size_t w2 = mnt753_affine_words(CURVE, MNT753_G2);
+  mnt753_vk* vk = nullptr;
+  check(mnt753_vk_create(CURVE, vk_elements, vk_elements + 24, vk_elements + 24 + w2, vk_elements + 24 + 2 * w2, num_inputs, &vk), "mnt753_vk_create");
+  std::vector<uint8_t> verdicts(n);
+  const int rc = mnt753_groth16_verify(vk, proofs, inputs, n, 0, verdicts.data(), nullptr);
+  mnt753_vk_destroy(vk);
+  if (rc < 0) check(rc, "mnt753_groth16_verify");
+  return verdicts;
+}
+
 template class mnt753_hip_impl<0>;
 template class mnt753_hip_impl<1>;

@@ -236,6 +236,53 @@ int mnt753_r1cs_check(mnt753_r1cs* r, const uint64_t* w, mnt753_check_report* ou
   return 0;
 }
 int mnt753_synth_scalars(int, uint64_t seed, size_t n, uint64_t* out) { for (size_t i = 0; i < 12 * n; ++i) out[i] = seed + i; return 0; }
+// the pairing and verification: sizes and argument checks only (no arithmetic: every proof is "accepted" unless MNT753_STUB_REJECT is set)
+struct mnt753_vk { int curve; size_t num_inputs; };
+size_t mnt753_gt_words(int curve) { return curve == 0 ? 48 : (curve == 1 ? 72 : 0); }
+int mnt753_pairing(int curve, const uint64_t* g1, const uint64_t* g2, size_t n, int, uint64_t* out, void*) {
+  if (curve < 0 || curve > 1 || (n && (!g1 || !g2 || !out))) return fail(MNT753_EINVAL, "pairing: bad argument");
+  if (!g_ndev) return fail(MNT753_ENODEV, "no device");
+  touch_ro(g1, 24 * n); touch_ro(g2, n * mnt753_affine_words(curve, MNT753_G2));
+  for (size_t i = 0; i < n * mnt753_gt_words(curve); ++i) out[i] = i;
+  return 0;
+}
+int mnt753_vk_create(int curve, const uint64_t* a, const uint64_t* b, const uint64_t* d, const uint64_t* abc, size_t num_inputs, mnt753_vk** out) {
+  if (curve < 0 || curve > 1 || !a || !b || !d || !abc || !out) return fail(MNT753_EINVAL, "vk_create: bad argument");
+  if (!g_ndev) return fail(MNT753_ENODEV, "no device");
+  touch_ro(a, 24); touch_ro(b, mnt753_affine_words(curve, MNT753_G2)); touch_ro(d, mnt753_affine_words(curve, MNT753_G2)); touch_ro(abc, 24 * (num_inputs + 1));
+  *out = new mnt753_vk{curve, num_inputs};
+  return 0;
+}
+int mnt753_vk_destroy(mnt753_vk* vk) { delete vk; return 0; }
+size_t mnt753_vk_num_inputs(const mnt753_vk* vk) { return vk ? vk->num_inputs : 0; }
+size_t mnt753_vk_coefficient_bytes(const mnt753_vk* vk) { return vk ? 1024 : 0; }
+int mnt753_vk_set_workspace_cap(mnt753_vk* vk, size_t) { return vk ? 0 : fail(MNT753_EINVAL, "vk_set_workspace_cap: bad argument"); }
+int mnt753_vk_gt(const mnt753_vk* vk, uint64_t* out) {
+  if (!vk || !out) return fail(MNT753_EINVAL, "vk_gt: bad argument");
+  for (size_t i = 0; i < mnt753_gt_words(vk->curve); ++i) out[i] = i;
+  return 0;
+}
+int mnt753_vk_serialize(const mnt753_vk* vk, uint8_t* buf, size_t cap, size_t* len) {
+  if (!vk || !len) return fail(MNT753_EINVAL, "vk_serialize: bad argument");
+  *len = 8 * mnt753_gt_words(vk->curve) + 16;
+  if (!buf) return 0;
+  if (cap < *len) return fail(MNT753_EINVAL, "vk_serialize: buffer too small");
+  for (size_t i = 0; i < *len; ++i) buf[i] = (uint8_t)i;
+  return 0;
+}
+int mnt753_vk_accumulate(const mnt753_vk* vk, const uint64_t* inputs, size_t n, uint64_t* out) {
+  if (!vk || (n && !out)) return fail(MNT753_EINVAL, "vk_accumulate: bad argument");
+  touch_ro(inputs, 12 * vk->num_inputs * n);
+  for (size_t i = 0; i < 24 * n; ++i) out[i] = i;
+  return 0;
+}
+int mnt753_groth16_verify(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int, uint8_t* verdicts, void*) {
+  if (!vk || (n && (!proofs || !verdicts))) return fail(MNT753_EINVAL, "groth16_verify: bad argument");
+  touch_ro(proofs, n * (48 + mnt753_affine_words(vk->curve, MNT753_G2))); touch_ro(inputs, 12 * vk->num_inputs * n);
+  const int reject = getenv("MNT753_STUB_REJECT") != nullptr;
+  for (size_t i = 0; i < n; ++i) verdicts[i] = reject ? 2 : 0;
+  return reject ? (int)n : 0;
+}
 int mnt753_group_generator(int curve, int group, uint64_t* out) {
   if (curve < 0 || curve > 1 || (group != MNT753_G1 && group != MNT753_G2) || !out) return fail(MNT753_EINVAL, "group_generator: bad argument");
   for (size_t i = 0; i < mnt753_affine_words(curve, group); ++i) out[i] = 1 + i;
