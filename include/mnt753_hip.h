@@ -465,8 +465,9 @@ size_t mnt753_gt_words(int curve);
 /* out_gt[i] = e(g1_affine[i], g2_affine[i]) for i < n: affine wire-format points; on_device != 0: the three pointers are device
  * pointers.  One lane group (2 or 3 lanes) per pairing; the call blocks until out_gt is complete.  Both arguments go through
  * mnt753_check_points first: a non-canonical coordinate or a point off its curve is MNT753_EINPUT and nothing is computed (no
- * subgroup test for G2, as there).  The identity in either argument gives GT one -- a DELIBERATE departure from libff, whose
- * precomputation runs on the identity's coordinates and returns a value without meaning. */
+ * subgroup test for G2: not checked unless the caller runs mnt753_check_subgroup first).  The identity in either argument gives GT
+ * one -- a DELIBERATE departure from libff, whose precomputation runs on the identity's coordinates and returns a value without
+ * meaning. */
 int mnt753_pairing(int curve, const uint64_t* g1_affine, const uint64_t* g2_affine, size_t n, int on_device, uint64_t* out_gt, void* stream);
 /* A Groth16 verification key on the device: the counterpart of libsnark's r1cs_gg_ppzksnark_verifier_process_vk
  * (r1cs_gg_ppzksnark.tcc:499-512).  alpha_g1, beta_g2, delta_g2, abc_g1 (num_inputs + 1 points): affine wire form in host memory --
@@ -505,12 +506,22 @@ int mnt753_vk_accumulate(const mnt753_vk* vk, const uint64_t* inputs, size_t n, 
  * >= r; such a proof runs the arithmetic on stand-in points, its neighbours in the wave are not disturbed.  The check is
  * FE(ML(A, B) ML(-acc, G2::one()) ML(-C, delta_g2)) == alpha_g1_beta_g2: one Miller loop over three pairs and one final
  * exponentiation; the same verdict as the reference's form (:409-414), from which it differs by a factor the final exponentiation
- * maps to one.  Subgroup membership of B is NOT checked, as in the reference.  Returns the number of proofs not
+ * maps to one.  Subgroup membership of B is NOT checked, as in the reference, unless mnt753_groth16_verify_ex is called with
+ * MNT753_VERIFY_CHECK_SUBGROUP (DESIGN.md sections 4.13 and 8).  Returns the number of proofs not
  * accepted (>= 0), or a negative MNT753_E* code.  The batch runs in chunks under mnt753_vk_set_workspace_cap (by default 2^16 proofs:
  * at most 2^16 (194 + 96 num_inputs) bytes, plus the staged copy of a chunk that arrives in host memory); one allocation of each
  * buffer per call.  With on_device, proofs and inputs must lie on the key's device (MNT753_EINVAL otherwise).  Only B is stepped
  * through the Miller loop; the coefficients of G2::one() and delta_g2 are read from the key.  Blocks until verdicts is complete. */
 int mnt753_groth16_verify(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int on_device, uint8_t* verdicts, void* stream);
+/* mnt753_groth16_verify with options.  flags == 0 is mnt753_groth16_verify itself (which is a call of this one and never returns
+ * verdict 3); an unknown bit is MNT753_EINVAL.  MNT753_VERIFY_CHECK_SUBGROUP: B of every proof is also tested for membership in G2, the
+ * order-r subgroup of the twist -- psi(B) == [t - 1] B on the running point the Miller loop holds anyway, an
+ * exact test per proof -- and a well-formed proof whose B fails it gets verdict 3, "B is not in the subgroup".  Precedence: malformed
+ * (1), then 3, then the pairing check (2).  The key's own beta_g2 and delta_g2 are NOT tested by this call or by mnt753_vk_create:
+ * mnt753_check_subgroup does that. */
+#define MNT753_VERIFY_CHECK_SUBGROUP 1u
+int mnt753_groth16_verify_ex(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int on_device, unsigned flags, uint8_t* verdicts,
+                             void* stream);
 
 /* ---- input validation (device) --------------------------------------------------------------------------
  * The reference prover trusts its files (unchecked fread, prover_reference_functions.cpp:48-116); what the reference HAS for the
@@ -522,13 +533,22 @@ int mnt753_groth16_verify(const mnt753_vk* vk, const uint64_t* proofs, const uin
  * whatever the scheduling.  n = 0 gives an all-zero report.  Null pointers / bad ids: MNT753_EINVAL; no device: MNT753_ENODEV.
  * MNT753_EINPUT is what the wrapper classes and main_hip make of a report with n_bad > 0 (main_hip: exit code 3). */
 #define MNT753_EINPUT (-7)            /* an input failed validation (wrapper / CLI level; the check calls themselves return 0) */
-enum { MNT753_BAD_NONE = 0, MNT753_BAD_NONCANONICAL = 1, MNT753_BAD_OFF_CURVE = 2, MNT753_BAD_UNSATISFIED = 3 };
+enum { MNT753_BAD_NONE = 0, MNT753_BAD_NONCANONICAL = 1, MNT753_BAD_OFF_CURVE = 2, MNT753_BAD_UNSATISFIED = 3, MNT753_BAD_NOT_IN_SUBGROUP = 4 };
 typedef struct { uint64_t n_bad, first_bad; uint32_t first_reason, reserved; } mnt753_check_report;
 /* n affine points in the wire format (on_device != 0: a device pointer).  Per point, the first that applies: a coordinate component
  * >= q -> MNT753_BAD_NONCANONICAL; all words of y zero -> the identity as read_g1 / read_g2 decode it (serialization.hpp:84-111),
  * well formed whatever x holds; y^2 != x^3 + a x + b (G2: the twist's a', b', mnt4753_init.cpp:122-123, mnt6753_init.cpp:133-136) ->
- * MNT753_BAD_OFF_CURVE.  is_well_formed() of the four groups; like it, no subgroup test for G2. */
+ * MNT753_BAD_OFF_CURVE.  is_well_formed() of the four groups; like it, no subgroup test for G2: that is not checked unless
+ * mnt753_check_subgroup is called (DESIGN.md sections 4.13 and 8). */
 int mnt753_check_points(int curve, int group, const uint64_t* affine, int on_device, size_t n, mnt753_check_report* out, void* stream);
+/* mnt753_check_points plus membership in the group of prime order r.  Arguments, n = 0 and the no-device behaviour as there.
+ * group == MNT753_G1: the cofactor is 1 on both curves, the result is mnt753_check_points' own and no further kernel runs.
+ * group == MNT753_G2: both twists have a large cofactor, a point on the twist need not be in G2.  One lane group (2 / 3 lanes) per
+ * point; per point the first that applies: non-canonical; the identity (good); off the twist; psi(P) != [t - 1] P ->
+ * MNT753_BAD_NOT_IN_SUBGROUP, with psi the twisted Frobenius and t - 1 = q - r the ate loop count -- an exact, deterministic test per
+ * point (no random combination: DESIGN.md section 4.13), some 376 doubling and 190 addition steps on the twist.  Meant for the B2
+ * entries of a parameter file and for beta_g2 / delta_g2 of a key. */
+int mnt753_check_subgroup(int curve, int group, const uint64_t* affine, int on_device, size_t n, mnt753_check_report* out, void* stream);
 /* n Fr elements of the curve: bad = the stored integer is >= r (MNT753_BAD_NONCANONICAL).  The field layer's contracts start from
  * canonical words (libff's Fp_model keeps them so, fp.tcc:161-186; a file can hold anything). */
 int mnt753_check_scalars(int curve, const uint64_t* fr, int on_device, size_t n, mnt753_check_report* out, void* stream);

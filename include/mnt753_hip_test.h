@@ -70,6 +70,14 @@ int mnt753_test_tower_op(int curve, int split, int op, const uint64_t* a, const 
 /* The UNREDUCED Miller value of n pairs (affine wire-format points, neither the identity; host pointers): what
  * mnt{4,6}753_ate_miller_loop returns before final_exponentiation, mnt753_gt_words words per pair. */
 int mnt753_test_miller_loop(int curve, int split, const uint64_t* g1_affine, const uint64_t* g2_affine, size_t n, uint64_t* out);
+/* The two halves of the subgroup test of G2 (csrc/pairing_kernels.hip.h) on n points of the twist (affine
+ * wire form, on the twist and not the identity, in G2 or not; host pointers), in the lane-split form the kernels run, so that a
+ * failure of mnt753_check_subgroup can be placed in the endomorphism or in the stepping:
+ * mnt753_test_g2_endomorphism: psi(P) = (x^q gamma_1^-2, y^q gamma_1^-3);
+ * mnt753_test_g2_loop_multiple: [t - 1] P, t - 1 = q - r the signed ate loop count, by the doubling and addition steps of the Miller
+ * loop alone; the identity (the incomplete steps ended with Z = 0) as zero words. */
+int mnt753_test_g2_endomorphism(int curve, const uint64_t* g2_affine, size_t n, uint64_t* out_affine);
+int mnt753_test_g2_loop_multiple(int curve, const uint64_t* g2_affine, size_t n, uint64_t* out_affine);
 
 #ifdef __cplusplus
 }

@@ -159,6 +159,12 @@ public:
   static check_report check_input_file(const char *params_path, const char *input_path);
   static check_report check_witness_file(const char *params_path, r1cs *cs, const char *witness_path);
   static const char *check_reason_text(int reason);
+  // Subgroup membership (mnt753_check_subgroup), opt-in: the overloads with subgroup = true send the B2 set
+  // through it instead of mnt753_check_points (the same tests first, then MNT753_BAD_NOT_IN_SUBGROUP; the G1 sets have cofactor 1).
+  // check_subgroup: n G2 points in host memory (wire words), e.g. beta_g2 | delta_g2 of a key, as one entry named "G2".
+  static check_report check_params(groth16_params *params, bool subgroup);
+  static check_report check_params_file(const char *params_path, bool subgroup);
+  static check_entry check_subgroup(const uint64_t *g2_affine, size_t n);
   // seconds the background loader of read_input needed until the whole input file was on the device (waits for it)
   static double input_load_seconds(groth16_input *input);
   // The pairing and Groth16 verification on the device (mnt753_pairing, mnt753_vk_create + mnt753_groth16_verify): extensions, the
@@ -167,6 +173,10 @@ public:
   // proofs = n x (A | B | C), inputs = n x num_inputs Fr; one verdict per proof: 0 accepted, 1 malformed, 2 the pairing check failed.
   static std::vector<uint64_t> pairing(const uint64_t *g1_affine, const uint64_t *g2_affine, size_t n);
   static std::vector<uint8_t> verify(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *proofs, const uint64_t *inputs, size_t n);
+  // with check_subgroup also verdict 3: B is not in the order-r subgroup of the twist (mnt753_groth16_verify_ex); the key's own G2
+  // elements are not tested by this call (check_subgroup above does that)
+  static std::vector<uint8_t> verify(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *proofs, const uint64_t *inputs, size_t n,
+                                     bool check_subgroup);
   // raw access for tests / tools
   static const uint64_t *G1_words(const G1 *a);
   static const uint64_t *G2_words(const G2 *a);

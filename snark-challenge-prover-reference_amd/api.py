@@ -18,6 +18,8 @@ class Mnt753Error(RuntimeError):
 
 
 BAD_NONE, BAD_NONCANONICAL, BAD_OFF_CURVE, BAD_UNSATISFIED = 0, 1, 2, 3
+BAD_NOT_IN_SUBGROUP = 4
+VERIFY_CHECK_SUBGROUP = 1
 
 
 class QapPlan(C.Structure):
@@ -145,6 +147,7 @@ def lib():
         "mnt753_r1cs_num_inputs": (sz, [vp]),
         "mnt753_r1cs_evaluate": (i, [vp, vp, vp, vp, vp, sz, vp]),
         "mnt753_check_points": (i, [i, i, vp, i, sz, C.POINTER(CheckReport), vp]),
+        "mnt753_check_subgroup": (i, [i, i, vp, i, sz, C.POINTER(CheckReport), vp]),
         "mnt753_check_scalars": (i, [i, vp, i, sz, C.POINTER(CheckReport), vp]),
         "mnt753_check_products": (i, [i, vp, vp, vp, sz, C.POINTER(CheckReport), vp]),
         "mnt753_r1cs_check": (i, [vp, vp, C.POINTER(CheckReport), vp]),
@@ -174,6 +177,7 @@ def lib():
         "mnt753_vk_serialize": (i, [vp, vp, sz, C.POINTER(C.c_size_t)]),
         "mnt753_vk_accumulate": (i, [vp, u64p, sz, u64p]),
         "mnt753_groth16_verify": (i, [vp, vp, vp, sz, i, vp, vp]),
+        "mnt753_groth16_verify_ex": (i, [vp, vp, vp, sz, i, C.c_uint, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)   # AttributeError here = the library does not export what the header declares
@@ -212,6 +216,8 @@ def test_lib():
         "mnt753_test_ext_raw": (i, [i, i, i, u32p, u32p, sz, u32p]),
         "mnt753_test_tower_op": (i, [i, i, i, u64p, u64p, sz, u64p]),
         "mnt753_test_miller_loop": (i, [i, i, u64p, u64p, sz, u64p]),
+        "mnt753_test_g2_endomorphism": (i, [i, u64p, sz, u64p]),
+        "mnt753_test_g2_loop_multiple": (i, [i, u64p, sz, u64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -587,6 +593,16 @@ def check_points(curve, group, affine, on_device=False, n=None, stream=None):
     rep = CheckReport()
     st = C.c_void_p(int(stream)) if stream else C.c_void_p()
     _check(lib().mnt753_check_points(curve, group, ptr, 1 if on_device else 0, cnt, C.byref(rep), st), "mnt753_check_points")
+    return _report(rep)
+
+
+def check_subgroup(curve, group, affine, on_device=False, n=None, stream=None):
+    """mnt753_check_subgroup: check_points plus membership in the subgroup of order r (G2: psi(P) == [t - 1] P per point; G1 has
+    cofactor 1) -> (n_bad, first_bad, reason of first_bad: BAD_*, BAD_NOT_IN_SUBGROUP among them)."""
+    ptr, cnt, keep = _input_ptr(affine, on_device, affine_words(curve, group), n)
+    rep = CheckReport()
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    _check(lib().mnt753_check_subgroup(curve, group, ptr, 1 if on_device else 0, cnt, C.byref(rep), st), "mnt753_check_subgroup")
     return _report(rep)
 
 
@@ -1023,6 +1039,7 @@ class VerificationKey:
         if a.size != 24 or b.size != affine_words(curve, G2) or d.size != b.size or abc.size < 24 or abc.size % 24:
             raise Mnt753Error("VerificationKey: element sizes do not fit the curve")
         self.num_inputs = abc.size // 24 - 1
+        self._g2 = np.concatenate([b, d])          # beta_g2 | delta_g2, for check_subgroup()
         self._h = C.c_void_p()
         _check(lib().mnt753_vk_create(curve, pa, pb, pd, pabc, self.num_inputs, C.byref(self._h)), "mnt753_vk_create")
 
@@ -1062,9 +1079,15 @@ class VerificationKey:
         _check(lib().mnt753_vk_accumulate(self._h, px, n, out.ctypes.data_as(C.POINTER(C.c_uint64))), "mnt753_vk_accumulate")
         return out
 
-    def verify(self, proofs, inputs, on_device=False, n=None, stream=None):
+    def check_subgroup(self):
+        """beta_g2 and delta_g2 of the key through check_subgroup -> (n_bad, first_bad: 0 = beta_g2, 1 = delta_g2, reason).  The key's
+        constructor (mnt753_vk_create) does not test membership itself."""
+        return check_subgroup(self.curve, G2, self._g2)
+
+    def verify(self, proofs, inputs, on_device=False, n=None, stream=None, check_subgroup=False):
         """proofs: n x (A | B | C) affine wire words, inputs: n x num_inputs Fr (numpy arrays, or device addresses with on_device and n)
-        -> numpy uint8 verdicts [n]: 0 accepted, 1 malformed, 2 the pairing check failed"""
+        -> numpy uint8 verdicts [n]: 0 accepted, 1 malformed, 2 the pairing check failed; with check_subgroup also 3: B is not in the
+        order-r subgroup of the twist (mnt753_groth16_verify_ex with MNT753_VERIFY_CHECK_SUBGROUP)"""
         pw = 48 + affine_words(self.curve, G2)
         pp, cnt, keep1 = _input_ptr(proofs, on_device, pw, n)
         if self.num_inputs:
@@ -1075,7 +1098,10 @@ class VerificationKey:
             pi = C.c_void_p()
         verdicts = np.zeros(cnt, dtype=np.uint8)
         st = C.c_void_p(int(stream)) if stream else C.c_void_p()
-        rc = lib().mnt753_groth16_verify(self._h, pp, pi, cnt, 1 if on_device else 0, C.c_void_p(verdicts.ctypes.data), st)
+        if check_subgroup:
+            rc = lib().mnt753_groth16_verify_ex(self._h, pp, pi, cnt, 1 if on_device else 0, VERIFY_CHECK_SUBGROUP, C.c_void_p(verdicts.ctypes.data), st)
+        else:
+            rc = lib().mnt753_groth16_verify(self._h, pp, pi, cnt, 1 if on_device else 0, C.c_void_p(verdicts.ctypes.data), st)
         if rc < 0:
             _check(rc, "mnt753_groth16_verify")
         return verdicts
@@ -1109,4 +1135,22 @@ def test_miller_loop(curve, split, P, Q):
     n = p.size // 24
     out = np.zeros((n, gt_words(curve)), dtype=np.uint64)
     _check(test_lib().mnt753_test_miller_loop(curve, split, pp, pq, n, out.ctypes.data_as(C.POINTER(C.c_uint64))), "mnt753_test_miller_loop")
+    return out
+
+
+def test_g2_endomorphism(curve, Q):
+    """mnt753_test_g2_endomorphism (test library): psi(Q) of n twist points [n, affine_words] -> the same shape"""
+    q, pq = _u64(Q)
+    n = q.size // affine_words(curve, G2)
+    out = np.zeros((n, affine_words(curve, G2)), dtype=np.uint64)
+    _check(test_lib().mnt753_test_g2_endomorphism(curve, pq, n, out.ctypes.data_as(C.POINTER(C.c_uint64))), "mnt753_test_g2_endomorphism")
+    return out
+
+
+def test_g2_loop_multiple(curve, Q):
+    """mnt753_test_g2_loop_multiple (test library): [t - 1] Q by the Miller loop's point steps, the identity as zero words"""
+    q, pq = _u64(Q)
+    n = q.size // affine_words(curve, G2)
+    out = np.zeros((n, affine_words(curve, G2)), dtype=np.uint64)
+    _check(test_lib().mnt753_test_g2_loop_multiple(curve, pq, n, out.ctypes.data_as(C.POINTER(C.c_uint64))), "mnt753_test_g2_loop_multiple")
     return out

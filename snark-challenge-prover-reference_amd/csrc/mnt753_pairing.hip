@@ -1,5 +1,5 @@
-// C ABI of the pairing and of Groth16 verification: mnt753_gt_words, mnt753_pairing, mnt753_vk_*, mnt753_groth16_verify
-// (include/mnt753_hip.h).  Kernels: pairing_kernels.hip.h.
+// C ABI of the pairing and of Groth16 verification: mnt753_gt_words, mnt753_pairing, mnt753_vk_*, mnt753_groth16_verify[_ex], and of
+// the subgroup test of a point set, mnt753_check_subgroup (include/mnt753_hip.h).  Kernels: pairing_kernels.hip.h.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
@@ -271,7 +271,14 @@ int mnt753_vk_accumulate(const mnt753_vk* vk, const uint64_t* inputs, size_t n, 
 }
 
 int mnt753_groth16_verify(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int on_device, uint8_t* verdicts, void* stream) {
-  if (!vk || (n && (!proofs || !verdicts || (vk->num_inputs && !inputs))) || n > MAX_PAIRINGS) return set_error(MNT753_EINVAL, "groth16_verify: bad argument");
+  return mnt753_groth16_verify_ex(vk, proofs, inputs, n, on_device, 0u, verdicts, stream);
+}
+
+int mnt753_groth16_verify_ex(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int on_device, unsigned flags, uint8_t* verdicts,
+                             void* stream) {
+  if (!vk || (n && (!proofs || !verdicts || (vk->num_inputs && !inputs))) || n > MAX_PAIRINGS || (flags & ~MNT753_VERIFY_CHECK_SUBGROUP))
+    return set_error(MNT753_EINVAL, "groth16_verify: bad argument");
+  const bool sub = (flags & MNT753_VERIFY_CHECK_SUBGROUP) != 0;
   if (int rc = require_device()) return rc;
   if (!n) return 0;
   OnDevice guard(vk->device);
@@ -310,16 +317,62 @@ int mnt753_groth16_verify(const mnt753_vk* vk, const uint64_t* proofs, const uin
     if (int rc = accumulate_on_device(vk, di, cnt, reinterpret_cast<uint64_t*>(buf.out), dev_bad, reinterpret_cast<uint32_t*>(buf.ints), st)) return rc;
     const uint32_t *p = reinterpret_cast<const uint32_t*>(dp), *acc = reinterpret_cast<const uint32_t*>(buf.out),
                    *key = reinterpret_cast<const uint32_t*>(vk->dev_key);
-    if (vk->curve == MNT753_CURVE_MNT4753)
-      hipLaunchKernelGGL((k_groth16_verify<Mnt4G2S, Mnt4G1>), dim3(blocks_for<Mnt4G2S::F>(cnt)), dim3(256), 0, st, p, acc, key, vk->dev_coeffs, dev_bad, dev_verdicts, (uint32_t)cnt);
-    else
-      hipLaunchKernelGGL((k_groth16_verify<Mnt6G2S, Mnt6G1>), dim3(blocks_for<Mnt6G2S::F>(cnt)), dim3(256), 0, st, p, acc, key, vk->dev_coeffs, dev_bad, dev_verdicts, (uint32_t)cnt);
+    if (vk->curve == MNT753_CURVE_MNT4753) {
+      const dim3 g(blocks_for<Mnt4G2S::F>(cnt)), b(256);
+      if (sub) hipLaunchKernelGGL((k_groth16_verify<Mnt4G2S, Mnt4G1, true>), g, b, 0, st, p, acc, key, vk->dev_coeffs, dev_bad, dev_verdicts, (uint32_t)cnt);
+      else hipLaunchKernelGGL((k_groth16_verify<Mnt4G2S, Mnt4G1>), g, b, 0, st, p, acc, key, vk->dev_coeffs, dev_bad, dev_verdicts, (uint32_t)cnt);
+    } else {
+      const dim3 g(blocks_for<Mnt6G2S::F>(cnt)), b(256);
+      if (sub) hipLaunchKernelGGL((k_groth16_verify<Mnt6G2S, Mnt6G1, true>), g, b, 0, st, p, acc, key, vk->dev_coeffs, dev_bad, dev_verdicts, (uint32_t)cnt);
+      else hipLaunchKernelGGL((k_groth16_verify<Mnt6G2S, Mnt6G1>), g, b, 0, st, p, acc, key, vk->dev_coeffs, dev_bad, dev_verdicts, (uint32_t)cnt);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(verdicts + first, dev_verdicts, cnt, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (size_t k = 0; k < cnt; ++k) rejected += verdicts[first + k] != 0;
   }
   return (int)rejected;
+}
+
+// Subgroup membership of n points.  G1 has cofactor 1 on both curves: mnt753_check_points' record is the answer.  G2: k_g2_subgroup,
+// one lane group per point, in launches of at most MAX_PAIRINGS points (logical lanes are 32-bit); the record carries the index.
+int mnt753_check_subgroup(int curve, int group, const uint64_t* affine, int on_device, size_t n, mnt753_check_report* out, void* stream) {
+  if (curve < 0 || curve > 1 || (group != MNT753_G1 && group != MNT753_G2) || !out || (n && !affine) || n > ((size_t)1 << 38))
+    return set_error(MNT753_EINVAL, "check_subgroup: bad argument");
+  if (group == MNT753_G1) return mnt753_check_points(curve, group, affine, on_device, n, out, stream);
+  if (int rc = require_device()) return rc;
+  *out = mnt753_check_report{0, 0, MNT753_BAD_NONE, 0};
+  if (!n) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t w2 = mnt753_affine_words(curve, MNT753_G2);
+  PairingBuffers buf;   // g2: the staged points, stand: the stand-in (the generator), out: the record
+  if (!on_device) {
+    if (int rc = alloc(&buf.g2, 8 * w2 * n)) return rc;
+    HIP_TRY(hipMemcpyAsync(buf.g2, affine, 8 * w2 * n, hipMemcpyHostToDevice, st));
+    affine = reinterpret_cast<const uint64_t*>(buf.g2);
+  }
+  if (int rc = alloc(&buf.stand, 8 * w2)) return rc;
+  if (int rc = alloc(&buf.out, sizeof(SubgroupReport))) return rc;
+  HIP_TRY(hipMemcpyAsync(buf.stand, curve == MNT753_CURVE_MNT4753 ? GEN_MNT4_G2 : GEN_MNT6_G2, 8 * w2, hipMemcpyHostToDevice, st));
+  SubgroupReport* rec = reinterpret_cast<SubgroupReport*>(buf.out);
+  hipLaunchKernelGGL(k_subgroup_report_init, dim3(1), dim3(1), 0, st, rec);
+  const uint32_t* stand = reinterpret_cast<const uint32_t*>(buf.stand);
+  for (size_t first = 0; first < n; first += MAX_PAIRINGS) {
+    const size_t cnt = n - first < MAX_PAIRINGS ? n - first : MAX_PAIRINGS;
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(affine + first * w2);
+    if (curve == MNT753_CURVE_MNT4753)
+      hipLaunchKernelGGL((k_g2_subgroup<Mnt4G2S>), dim3(blocks_for<Mnt4G2S::F>(cnt)), dim3(256), 0, st, p, stand, (uint32_t)cnt, (unsigned long long)first, rec);
+    else
+      hipLaunchKernelGGL((k_g2_subgroup<Mnt6G2S>), dim3(blocks_for<Mnt6G2S::F>(cnt)), dim3(256), 0, st, p, stand, (uint32_t)cnt, (unsigned long long)first, rec);
+  }
+  HIP_TRY(hipGetLastError());
+  SubgroupReport host;
+  HIP_TRY(hipMemcpyAsync(&host, rec, sizeof(host), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  out->n_bad = host.n_bad;
+  out->first_bad = host.n_bad ? (uint64_t)(host.key >> 3) : 0;
+  out->first_reason = host.n_bad ? (uint32_t)(host.key & 7u) : (uint32_t)MNT753_BAD_NONE;
+  return 0;
 }
 
 }  // extern "C"

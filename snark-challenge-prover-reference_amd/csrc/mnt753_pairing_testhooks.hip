@@ -73,7 +73,34 @@ int run_miller(const uint64_t* g1, const uint64_t* g2, size_t n, uint64_t* out) 
   HIP_TRY(hipMemcpy(out, dout.p, b2, hipMemcpyDeviceToHost));
   return 0;
 }
+
+// one half of the subgroup test on n points of the twist: psi(P) (what = 0) or [t - 1] P (what = 1), in the lane-split form
+template <class C>
+int run_subgroup_half(int what, const uint64_t* g2, size_t n, uint64_t* out) {
+  using F = typename C::F;
+  const size_t bytes = 8 * 24 * (size_t)F::DEG * n;
+  DevBuf din, dout;
+  HIP_TRY(hipMalloc(&din.p, bytes)); HIP_TRY(hipMalloc(&dout.p, bytes));
+  HIP_TRY(hipMemcpy(din.p, g2, bytes, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL((k_g2_subgroup_half<C>), dim3(blocks_for<F>(n)), dim3(256), 0, 0, what, din.p, dout.p, (uint32_t)n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+int subgroup_half(const char* name, int what, int curve, const uint64_t* g2_affine, size_t n, uint64_t* out) {
+  if (curve < 0 || curve > 1 || (n && (!g2_affine || !out)) || n > 0xffffffu) return set_error(MNT753_EINVAL, name);
+  if (int rc = require_device()) return rc;
+  if (n == 0) return 0;
+  return curve == MNT753_CURVE_MNT4753 ? run_subgroup_half<Mnt4G2S>(what, g2_affine, n, out) : run_subgroup_half<Mnt6G2S>(what, g2_affine, n, out);
+}
 }  // namespace
+
+extern "C" int mnt753_test_g2_endomorphism(int curve, const uint64_t* g2_affine, size_t n, uint64_t* out_affine) {
+  return subgroup_half("test_g2_endomorphism: bad argument", 0, curve, g2_affine, n, out_affine);
+}
+extern "C" int mnt753_test_g2_loop_multiple(int curve, const uint64_t* g2_affine, size_t n, uint64_t* out_affine) {
+  return subgroup_half("test_g2_loop_multiple: bad argument", 1, curve, g2_affine, n, out_affine);
+}
 
 extern "C" int mnt753_test_tower_op(int curve, int split, int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
   const int k = curve == MNT753_CURVE_MNT4753 ? 4 : 6;

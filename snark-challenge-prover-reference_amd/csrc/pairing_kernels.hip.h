@@ -151,6 +151,84 @@ struct Ate {
     line_add(f, p, mx, my, my2);
   }
 
+  // ---- subgroup membership on the twist ----------------------------------------------------------------
+  // psi = twist^-1 o Frobenius_q o twist on E'(F): psi(x, y) = (x^q gamma_1^-2, y^q gamma_1^-3).  x^q in F is component c times
+  // gamma_1^(2 c), the frob[1][2 c] the tower's Frobenius already uses; the two constants lie in Fq (tools/gen_constants.py asserts
+  // it, and psi(G2::one()) = [q - r] G2::one(), which fixes the sign of the y constant).  The product by the constant is a product
+  // of F with the embedded constant: no further instance of the multiplier.
+  static TW_FN void endo(FE& sx, FE& sy, const FE& qx, const FE& qy) {
+    B k;
+    FE c, t;
+    X::template frob_scale<1, 0>(t, qx);
+    fp_const_limbs(k, PAIRC[CURVE].psi_x);
+    X::embed(c, k, 0);
+    X::mul(sx, t, c);
+    X::template frob_scale<1, 0>(t, qy);
+    fp_const_limbs(k, PAIRC[CURVE].psi_y);
+    X::embed(c, k, 0);
+    X::mul(sy, t, c);
+  }
+  static TW_FN bool f_equal(const FE& a, const FE& b) {
+    FE d;
+    X::sub(d, a, b);
+    return F::is_zero(d);
+  }
+  // Q in G2  <=>  psi(Q) = [t - 1] Q, t - 1 = q - r the signed loop count: psi satisfies X^2 - t X + q, so psi(Q) = [t - 1] Q gives
+  // [(t - 1)^2 - t (t - 1) + q] Q = [r] Q = O, and G2 is the eigenspace of Frobenius with eigenvalue q = t - 1 (mod r).  Exact, per
+  // point, with the 377-bit multiplier the Miller loop steps anyway.  The two predicates take the running point R = [|t - 1|] Q as
+  // the bit loop of the Miller loop leaves it, and (sx, sy) = psi(Q).
+  // Z = 0 is tested explicitly and means NOT in the subgroup.  dbl_step / add_step are incomplete formulas: a Q with a component of
+  // small order in the cofactor group can meet R = O, or R = +-Q at an addition, in mid-loop, and then Z becomes 0.  Z = 0 is a
+  // sink of both steps (doubling: Z3 = 2 Y Z; addition: T = 0 gives H = -X, I = X^2 and Z3 = (Z + H)^2 - T - I = 0), every later
+  // coordinate is then without meaning, and an all-zero R would satisfy 0 == 0 below.  A member of G2 never meets the exceptional
+  // cases: they need m Q in {O, +-Q} for a prefix m of the loop count, 1 < m < 2^377, and Q has prime order r > 2^752.
+  // Positive loop count (MNT6753): R = [t - 1] Q projectively against psi(Q): X == sx T and Y == sy Z T with T = Z^2.  No inversion.
+  static TW_FN bool run_equals(const Run& R, const FE& sx, const FE& sy) {
+    FE a, b;
+    const bool z0 = F::is_zero(R.Z);
+    X::mul(a, sx, R.T);
+    const bool ex = f_equal(R.X, a);
+    X::mul(b, R.Z, R.T);
+    X::mul(a, sy, b);
+    const bool ey = f_equal(R.Y, a);
+    return !z0 && ex && ey;
+  }
+  // Negative loop count (MNT4753): [t - 1] Q = -R, which minus_r_affine has made affine for the closing step: (mx, my).  Taken BEFORE
+  // the closing addition (after it R is O).  rz: R.Z as the bit loop left it.
+  static TW_FN bool affine_equals(const FE& rz, const FE& mx, const FE& my, const FE& sx, const FE& sy) {
+    const bool z0 = F::is_zero(rz);
+    const bool ex = f_equal(mx, sx);
+    const bool ey = f_equal(my, sy);
+    return !z0 && ex && ey;
+  }
+  // R <- [|t - 1|] Q from R = Q: the point stepping of the Miller loop alone (no G1 side, no tower, no line values).  dbl_step's H, J
+  // and L -- three squarings the point does not need -- are computed and dropped: the loop stays the one the pairing runs.
+  static HD void step_loop(Run& R, const FE& qx, const FE& qy) {
+    FE qy2, H, C4, J, L, L1;
+    X::sqr(qy2, qy);
+    R.X = qx; R.Y = qy; X::one(R.Z); X::one(R.T);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+    for (int i = PAIRC[CURVE].loop_bits - 2; i >= 0; --i) {
+      dbl_step(R, H, C4, J, L);
+      if ((PAIRC[CURVE].loop_count[i >> 5] >> (i & 31)) & 1u) add_step(qx, qy, qy2, R, L1);
+    }
+  }
+  // the whole test of one point (not the identity, on the twist)
+  static HD bool in_subgroup(const FE& qx, const FE& qy) {
+    Run R;
+    FE sx, sy;
+    step_loop(R, qx, qy);
+    endo(sx, sy, qx, qy);
+    if (PAIRC[CURVE].loop_neg) {
+      FE mx, my, my2;
+      minus_r_affine(mx, my, my2, R);
+      return affine_equals(R.Z, mx, my, sx, sy);
+    }
+    return run_equals(R, sx, sy);
+  }
+
   template <int K>
   static HD void miller_loop(TE& f, Pair (&p)[K]) {
     T::one(f);
@@ -395,12 +473,15 @@ __device__ __attribute__((noinline)) void stored_line_add(typename Tower<typenam
   X::neg(g.c1, t);
   Tower<F>::mul(f, f, g);
 }
-// The verifier's Miller loop: one pair stepped as it goes (p) and two pairs read from a key's stored coefficients, one squaring
-template <class C>
-__device__ __forceinline__ void miller_loop_verify(typename Tower<typename C::F>::E& f, typename Ate<C>::Pair& p, const StoredPair<C>& s1, const uint32_t* c1,
+// The verifier's Miller loop: one pair stepped as it goes (p) and two pairs read from a key's stored coefficients, one squaring.
+// SUB: also the subgroup test of the stepped pair's G2 point, on the running point the loop holds anyway (Ate<C>::run_equals /
+// affine_equals); returns its answer (true without SUB).
+template <class C, bool SUB = false>
+__device__ __forceinline__ bool miller_loop_verify(typename Tower<typename C::F>::E& f, typename Ate<C>::Pair& p, const StoredPair<C>& s1, const uint32_t* c1,
                                                    const StoredPair<C>& s2, const uint32_t* c2) {
   using A = Ate<C>;
   using T = Tower<typename C::F>;
+  bool member = true;
   T::one(f);
 #pragma unroll 1
   for (int i = PAIRC[A::CURVE].loop_bits - 2; i >= 0; --i) {
@@ -416,11 +497,24 @@ __device__ __forceinline__ void miller_loop_verify(typename Tower<typename C::F>
     }
   }
   if (PAIRC[A::CURVE].loop_neg) {
-    A::line_close(f, p);
+    if constexpr (SUB) {
+      typename A::FE sx, sy, mx, my, my2;
+      A::endo(sx, sy, p.qx, p.qy);
+      A::minus_r_affine(mx, my, my2, p.R);
+      member = A::affine_equals(p.R.Z, mx, my, sx, sy);
+      A::line_add(f, p, mx, my, my2);            // line_close, with -R affine in hand
+    } else {
+      A::line_close(f, p);
+    }
     stored_line_add<C>(f, s1, c1);
     stored_line_add<C>(f, s2, c2);
     T::inv(f, f);
+  } else if constexpr (SUB) {
+    typename A::FE sx, sy;
+    A::endo(sx, sy, p.qx, p.qy);
+    member = A::run_equals(p.R, sx, sy);
   }
+  return member;
 }
 
 // ---- Groth16 verification ---------------------------------------------------------------------------------------------------------
@@ -580,8 +674,10 @@ __global__ void __launch_bounds__(256, 1) k_vk_accumulate(const uint32_t* __rest
 // key: stand-in G1 | G2::one() | delta_g2 | e(alpha, beta), wire words.  acc: mnt753_vk_accumulate's output for these proofs.
 // bad[t] != 0 on entry: an input of proof t is >= r.  A malformed proof -- a non-canonical coordinate, a point off its curve, an
 // identity among A, B, C or acc, such an input -- runs the arithmetic on the stand-in points (the generators), so that its neighbours
-// in the wave see nothing of it, and its verdict is 1.  No subgroup test of B.
-template <class C, class C1>
+// in the wave see nothing of it, and its verdict is 1.  No subgroup test of B unless SUB: then a well-formed
+// proof whose B is not in the order-r subgroup of the twist gets verdict 3, before the pairing check is looked at (the pairing is
+// bilinear on G2 only); a malformed proof steps the generator, which is in G2, and stays 1.
+template <class C, class C1, bool SUB = false>
 __global__ void __launch_bounds__(256, 1) k_groth16_verify(const uint32_t* __restrict__ proofs, const uint32_t* __restrict__ acc, const uint32_t* __restrict__ key,
                                                           const uint32_t* __restrict__ coeffs, const uint8_t* __restrict__ bad, uint8_t* __restrict__ verdicts, uint32_t n) {
   using A = Ate<C>;
@@ -634,7 +730,7 @@ __global__ void __launch_bounds__(256, 1) k_groth16_verify(const uint32_t* __res
   stored_setup<C>(s2, cx, cy, qx, qy);
   typename A::TE f, r;
   constexpr int CW = ate_coeff_words<C>();
-  miller_loop_verify<C>(f, p, s1, coeffs, s2, coeffs + CW);
+  const bool member = miller_loop_verify<C, SUB>(f, p, s1, coeffs, s2, coeffs + CW);
   A::final_exponentiation(r, f);
   bool same = true;
 #pragma unroll 1
@@ -653,7 +749,91 @@ __global__ void __launch_bounds__(256, 1) k_groth16_verify(const uint32_t* __res
     }
   }
   same = group_all<F>(same);
-  if (lane_comp<F>() == 0) verdicts[t] = malformed ? 1 : (same ? 0 : 2);
+  if (lane_comp<F>() == 0) verdicts[t] = malformed ? 1 : (!member ? 3 : (same ? 0 : 2));
+}
+
+// ---- subgroup membership of a point set ----------------------------------------------------------------------------------------------
+// The report record of k_g2_subgroup: number of bad points and the lowest key, key = index << 3 | reason (the reasons of
+// include/mnt753_hip.h go up to MNT753_BAD_NOT_IN_SUBGROUP = 4; mnt753_validate.hip's own record keeps two bits), all ones = good.
+struct SubgroupReport {
+  unsigned long long n_bad, key;
+};
+__global__ void k_subgroup_report_init(SubgroupReport* rec) {
+  rec->n_bad = 0;
+  rec->key = ~0ull;
+}
+// Per point (n affine wire-format points of the twist, point base + t by lane group t, lane mapping as k_pairing), the first that
+// applies: a coordinate component >= q -> 1 (non-canonical); all y words zero -> the identity, good; off the twist -> 2; psi(Q) !=
+// [t - 1] Q -> 4 (Ate<C>::in_subgroup).  A point that fails an earlier test, and the identity, steps the stand-in (stand_g2: the
+// generator), as a malformed proof does in the verifier.  The record does not depend on scheduling: one lane per group holds the
+// point's key, a wave's count and lowest key come from a ballot (indices grow with the lane, so the lowest flagged lane holds the
+// wave's minimum), and a wave that found something issues one 64-bit atomic add and one 64-bit atomic min.
+template <class C>
+__global__ void __launch_bounds__(256, 1) k_g2_subgroup(const uint32_t* __restrict__ g2, const uint32_t* __restrict__ stand_g2, uint32_t n,
+                                                       unsigned long long base, SubgroupReport* __restrict__ rec) {
+  using A = Ate<C>;
+  using F = typename C::F;
+  constexpr int M = F::MOD;
+  constexpr int W2 = wire_coord_words<C>();
+  const uint32_t t = logical_lane<F>();
+  if (t == 0xffffffffu || t >= n) return;        // (all lanes of a group leave together)
+  const uint32_t* p2 = g2 + (size_t)t * 2 * W2;
+  const int comp = (int)lane_comp<F>();
+  bool nc = false;
+  if constexpr (F::LANES == 1) {
+    for (int k = 0; k < 2 * F::DEG; ++k) nc |= wire_noncanonical<M>(p2 + 24 * k);
+  } else {
+    nc = wire_noncanonical<M>(p2 + 24 * comp) || wire_noncanonical<M>(p2 + W2 + 24 * comp);
+  }
+  const bool noncanon = !group_all<F>(!nc);
+  const bool ident = wire_y_is_zero<F>(p2 + W2);
+  typename A::FE qx, qy;
+  wire_load<F>(qx, p2);
+  wire_load<F>(qy, p2 + W2);
+  uint32_t reason = 0;                           // MNT753_BAD_NONE
+  if (noncanon) reason = 1;                      // MNT753_BAD_NONCANONICAL
+  else if (!ident && !g2_on_curve<C>(qx, qy)) reason = 2;   // MNT753_BAD_OFF_CURVE
+  if (reason != 0 || ident) {
+    wire_load<F>(qx, stand_g2);
+    wire_load<F>(qy, stand_g2 + W2);
+  }
+  const bool member = A::in_subgroup(qx, qy);
+  if (reason == 0 && !ident && !member) reason = 4;   // MNT753_BAD_NOT_IN_SUBGROUP
+  const bool flag = comp == 0 && reason != 0;
+  const unsigned long long bad = __ballot(flag);
+  if (bad && (int)(threadIdx.x & 63u) == __ffsll(bad) - 1) {
+    atomicAdd(&rec->n_bad, (unsigned long long)__popcll(bad));
+    atomicMin(&rec->key, ((base + t) << 3) | reason);
+  }
+}
+
+// The two halves of the test for n points each (test hooks): what == 0: psi(P); what == 1: [t - 1] P, affine wire words, the identity
+// (the stepping ended with Z = 0) as zero words.  Points on the twist, not the identity.
+template <class C>
+__global__ void __launch_bounds__(256, 1) k_g2_subgroup_half(int what, const uint32_t* __restrict__ g2, uint32_t* __restrict__ out, uint32_t n) {
+  using A = Ate<C>;
+  using F = typename C::F;
+  using X = FX<F>;
+  constexpr int W2 = wire_coord_words<C>();
+  const uint32_t t = logical_lane<F>();
+  if (t == 0xffffffffu || t >= n) return;
+  typename A::FE qx, qy, rx, ry;
+  wire_load<F>(qx, g2 + (size_t)t * 2 * W2);
+  wire_load<F>(qy, g2 + (size_t)t * 2 * W2 + W2);
+  if (what == 0) {
+    A::endo(rx, ry, qx, qy);
+  } else {
+    typename A::Run R;
+    typename A::FE my2;
+    A::step_loop(R, qx, qy);
+    const bool z0 = F::is_zero(R.Z);
+    A::minus_r_affine(rx, ry, my2, R);           // -R affine: [t - 1] P where the loop count is negative
+    if (!PAIRC[A::CURVE].loop_neg) X::neg(ry, ry);
+    if (z0) { X::zero(rx); X::zero(ry); }
+  }
+  uint32_t* dst = out + (size_t)t * 2 * W2;
+  wire_store<F>(dst, rx);
+  wire_store<F>(dst + W2, ry);
 }
 #endif  // __HIPCC__
 

@@ -5,6 +5,7 @@
 // ./main_hip <curve> generate <r1cs> <out_dir> [--randomness <file>] [--mixed-radix]   (a Groth16 key for the system: params.bin, keys.bin, vk_elements.bin, r1cs.bin)
 // ./main_hip <curve> complete <keys> <input|witness> <challenge_proof> <full_proof> [--s-file <Fr> | --s-seed N]
 // ./main_hip <curve> check <params> [<input>] | check-r1cs <params> <r1cs> <witness>      (validation only; exit code 3 = malformed input)
+//            check --subgroup: B2 must also lie in the order-r subgroup of the twist; verify --check-subgroup: the key's G2 elements and every B
 //            --validate on compute / compute-r1cs / complete: the same checks before proving; a failing job writes nothing
 //            --mixed-radix on compute / compute-r1cs / complete (or MNT753_MIXED_RADIX=1): MNT6753 domains of 2^a 5^b elements, up to 819200
 // Exit codes: 0 success, 1 device / I/O / self-test failure, 2 usage, 3 an input failed validation.
@@ -329,11 +330,12 @@ int run_prover(const char* params_path, const std::vector<std::pair<std::string,
 // ./main_hip <curve> check-r1cs <params> <r1cs> <witness>  the same for the parameters, and the witness against the constraint system
 // One line per set on stdout; exit code 0 if everything is well formed, 3 if not.  A one-shot by nature: the files are streamed to the
 // device and checked there -- no base sets, no window tables, no level buffers, no evaluation domain, no warm-up.
+// --subgroup: B2 also goes through the subgroup test of G2 (mnt753_check_subgroup): "B2: 1 bad, first at 3: not in the subgroup"
 template <typename B>
-int run_check(const char* params_path, const char* input_path, const char* r1cs_path) {
+int run_check(const char* params_path, const char* input_path, const char* r1cs_path, bool subgroup) {
   if (g_gpus > 0) B::use_devices(g_gpus);
   B::init_public_params();
-  bool ok = print_report<B>(B::check_params_file(params_path));
+  bool ok = print_report<B>(subgroup ? B::check_params_file(params_path, true) : B::check_params_file(params_path));
   if (r1cs_path) {
     auto cs = B::read_r1cs(r1cs_path);
     try { ok = print_report<B>(B::check_witness_file(params_path, cs, input_path)) && ok; } catch (...) { B::delete_r1cs(cs); throw; }
@@ -594,7 +596,9 @@ static int generate_key(int curve, const char* r1cs_path, const char* out_dir, c
 
 // `main_hip <curve> vk <vk_elements.bin> <out>` writes the complete verification key (the reference's vk.txt: mnt753_vk_serialize);
 // `main_hip <curve> verify <vk_elements.bin> <input_or_witness> <proof> [<proof> ...]` prints VERIFIED or REJECTED per proof
-// (B::verify = mnt753_vk_create + mnt753_groth16_verify) and exits 0 if all are accepted, 3 otherwise.  vk_elements.bin: alpha_g1 | beta_g2 | delta_g2 | ABC_g1, so
+// (B::verify = mnt753_vk_create + mnt753_groth16_verify) and exits 0 if all are accepted, 3 otherwise.  With --check-subgroup the key's
+// beta_g2 and delta_g2 go through B::check_subgroup first (a bad key: a message naming the element, exit 3, nothing verified), the
+// proofs are verified with MNT753_VERIFY_CHECK_SUBGROUP, and a B outside G2 prints REJECTED (B not in the subgroup).  vk_elements.bin: alpha_g1 | beta_g2 | delta_g2 | ABC_g1, so
 // its size gives num_inputs; the input (or witness) file starts with 1 and the num_inputs public inputs.
 static bool read_all_words(const char* path, std::vector<uint64_t>& out) {
   FILE* f = fopen(path, "rb");
@@ -609,7 +613,7 @@ static bool read_all_words(const char* path, std::vector<uint64_t>& out) {
   fclose(f);
   return true;
 }
-static int vk_command(int curve, bool verify, const std::vector<const char*>& pos) {
+static int vk_command(int curve, bool verify, const std::vector<const char*>& pos, bool check_subgroup = false) {
   const size_t w2 = mnt753_affine_words(curve, MNT753_G2);
   std::vector<uint64_t> el;
   if (!read_all_words(pos[0], el)) return 1;
@@ -639,11 +643,28 @@ static int vk_command(int curve, bool verify, const std::vector<const char*>& po
     for (size_t k = 0; k < n; ++k) per_proof.insert(per_proof.end(), inputs.begin() + 12, inputs.end());
     std::vector<uint8_t> verdicts;
     try {
-      verdicts = curve == 0 ? mnt4753_hip::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n)
-                            : mnt6753_hip::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n);
+      if (check_subgroup) {
+        // beta_g2 | delta_g2 lie side by side in the file
+        uint64_t n_bad, first_bad;
+        int reason;
+        if (curve == 0) { const auto e = mnt4753_hip::check_subgroup(el.data() + 24, 2); n_bad = e.n_bad; first_bad = e.first_bad; reason = e.reason; }
+        else { const auto e = mnt6753_hip::check_subgroup(el.data() + 24, 2); n_bad = e.n_bad; first_bad = e.first_bad; reason = e.reason; }
+        if (n_bad) {
+          fprintf(stderr, "main_hip: %s of the key: %s\n", first_bad == 0 ? "beta_g2" : "delta_g2", mnt4753_hip::check_reason_text(reason));
+          return 3;
+        }
+        verdicts = curve == 0 ? mnt4753_hip::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n, true)
+                              : mnt6753_hip::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n, true);
+      } else {
+        verdicts = curve == 0 ? mnt4753_hip::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n)
+                              : mnt6753_hip::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n);
+      }
     } catch (const std::exception& e) { fprintf(stderr, "main_hip: %s\n", e.what()); return 1; }
     int bad = 0;
-    for (size_t k = 0; k < n; ++k) { printf("%s\n", verdicts[k] == 0 ? "VERIFIED" : "REJECTED"); bad += verdicts[k] != 0; }
+    for (size_t k = 0; k < n; ++k) {
+      printf("%s\n", verdicts[k] == 0 ? "VERIFIED" : (verdicts[k] == 3 ? "REJECTED (B not in the subgroup)" : "REJECTED"));
+      bad += verdicts[k] != 0;
+    }
     return bad ? 3 : 0;
   }
   mnt753_vk* vk = nullptr;
@@ -670,17 +691,21 @@ int main(int argc, char** argv) {
     const int curve = !strcmp(argv[1], "MNT4753") ? 0 : (!strcmp(argv[1], "MNT6753") ? 1 : -1);
     if (curve < 0) { fprintf(stderr, "unknown curve %s\n", argv[1]); return 2; }
     std::vector<const char*> pos;
+    bool check_subgroup = false;
     for (int i = 3; i < argc; ++i) {
+      if (verify && !strcmp(argv[i], "--check-subgroup")) { check_subgroup = true; continue; }
       if (argv[i][0] == '-') { fprintf(stderr, "main_hip: unknown option %s\n", argv[i]); return 2; }
       pos.push_back(argv[i]);
     }
     if (verify ? pos.size() < 3 : pos.size() != 2) {
-      fprintf(stderr, "usage: %s MNT4753|MNT6753 vk <vk_elements.bin> <out>\n       %s MNT4753|MNT6753 verify <vk_elements.bin> <input_or_witness> <proof> [<proof> ...]\n"
+      fprintf(stderr, "usage: %s MNT4753|MNT6753 vk <vk_elements.bin> <out>\n       %s MNT4753|MNT6753 verify <vk_elements.bin> <input_or_witness> <proof> [<proof> ...] [--check-subgroup]\n"
                       "  vk: writes the complete verification key (with the GT element e(alpha_g1, beta_g2)) in the reference's vk.txt format.\n"
-                      "  verify: prints VERIFIED or REJECTED per proof; exit code 0 if every proof is accepted, 3 otherwise.\n", argv[0], argv[0]);
+                      "  verify: prints VERIFIED or REJECTED per proof; exit code 0 if every proof is accepted, 3 otherwise.\n"
+                      "  --check-subgroup: beta_g2 and delta_g2 of the key and B of every proof must lie in G2, the order-r subgroup of the twist;\n"
+                      "    a key that fails is named and nothing is verified (exit 3), such a proof prints REJECTED (B not in the subgroup).\n", argv[0], argv[0]);
       return 2;
     }
-    return vk_command(curve, verify, pos);
+    return vk_command(curve, verify, pos, check_subgroup);
   }
   if (argc >= 3 && !strcmp(argv[2], "generate")) {
     const int curve = !strcmp(argv[1], "MNT4753") ? 0 : (!strcmp(argv[1], "MNT6753") ? 1 : -1);
@@ -756,20 +781,23 @@ int main(int argc, char** argv) {
   if (argc >= 3 && (!strcmp(argv[2], "check") || !strcmp(argv[2], "check-r1cs"))) {
     const bool with_r1cs = !strcmp(argv[2], "check-r1cs");
     std::vector<const char*> pos;
+    bool subgroup = false;
     for (int i = 3; i < argc; ++i) {
       if (!strcmp(argv[i], "--gpus") && i + 1 < argc) { g_gpus = atoi(argv[++i]); continue; }
+      if (!with_r1cs && !strcmp(argv[i], "--subgroup")) { subgroup = true; continue; }
       if (argv[i][0] == '-') { fprintf(stderr, "main_hip: unknown option %s\n", argv[i]); return 2; }
       pos.push_back(argv[i]);
     }
     if (with_r1cs ? pos.size() != 3 : (pos.empty() || pos.size() > 2)) {
-      fprintf(stderr, "usage: %s MNT4753|MNT6753 check <params> [<input>] [--gpus N]\n       %s MNT4753|MNT6753 check-r1cs <params> <r1cs> <witness> [--gpus N]\n", argv[0], argv[0]);
+      fprintf(stderr, "usage: %s MNT4753|MNT6753 check <params> [<input>] [--subgroup] [--gpus N]\n       %s MNT4753|MNT6753 check-r1cs <params> <r1cs> <witness> [--gpus N]\n"
+                      "  --subgroup: the B2 points must also lie in G2, the order-r subgroup of the twist (\"not in the subgroup\")\n", argv[0], argv[0]);
       return 2;
     }
     const char* input = with_r1cs ? pos[2] : (pos.size() > 1 ? pos[1] : nullptr);
     const char* r1cs = with_r1cs ? pos[1] : nullptr;
     try {
-      if (!strcmp(argv[1], "MNT4753")) return run_check<mnt4753_hip>(pos[0], input, r1cs);
-      if (!strcmp(argv[1], "MNT6753")) return run_check<mnt6753_hip>(pos[0], input, r1cs);
+      if (!strcmp(argv[1], "MNT4753")) return run_check<mnt4753_hip>(pos[0], input, r1cs, subgroup);
+      if (!strcmp(argv[1], "MNT6753")) return run_check<mnt6753_hip>(pos[0], input, r1cs, subgroup);
       fprintf(stderr, "unknown curve %s\n", argv[1]);
       return 2;
     } catch (const std::exception& e) {

@@ -1252,6 +1252,7 @@ template <int CURVE> const char* HIP_B::check_reason_text(int reason) {
     case MNT753_BAD_NONCANONICAL: return "not canonical";
     case MNT753_BAD_OFF_CURVE: return "off curve";
     case MNT753_BAD_UNSATISFIED: return "not satisfied";
+    case MNT753_BAD_NOT_IN_SUBGROUP: return "not in the subgroup";
     default: return "unknown reason";
   }
 }
@@ -1284,7 +1285,8 @@ template <class Report> void add_entry(Report& rep, const char* set, size_t size
   rep.sets[rep.n_sets++] = {set, size, r.n_bad, r.first_bad, (int)r.first_reason};
 }
 }  // namespace
-template <int CURVE> typename HIP_B::check_report HIP_B::check_params_file(const char* path) {
+template <int CURVE> typename HIP_B::check_report HIP_B::check_params_file(const char* path) { return check_params_file(path, false); }
+template <int CURVE> typename HIP_B::check_report HIP_B::check_params_file(const char* path, bool subgroup) {
   size_t d = 0, m = 0;
   params_header(path, CURVE, &d, &m);
   const size_t g1w = mnt753_affine_words(CURVE, MNT753_G1), g2w = mnt753_affine_words(CURVE, MNT753_G2);
@@ -1305,7 +1307,11 @@ template <int CURVE> typename HIP_B::check_report HIP_B::check_params_file(const
       CheckBlock blk(8 * s.words * (hi - lo));
       check(mnt753_load_file_to_device(path, s.off + 8 * s.words * lo, 8 * s.words * (hi - lo), blk.ptr), "mnt753_load_file_to_device");
       mnt753_check_report r;
-      check(mnt753_check_points(CURVE, s.group, reinterpret_cast<const uint64_t*>(blk.ptr), 1, hi - lo, &r, nullptr), "mnt753_check_points");
+      // with `subgroup` the G2 set goes through mnt753_check_subgroup: the same tests first, then membership in G2 (G1: cofactor 1)
+      if (subgroup && s.group == MNT753_G2)
+        check(mnt753_check_subgroup(CURVE, s.group, reinterpret_cast<const uint64_t*>(blk.ptr), 1, hi - lo, &r, nullptr), "mnt753_check_subgroup");
+      else
+        check(mnt753_check_points(CURVE, s.group, reinterpret_cast<const uint64_t*>(blk.ptr), 1, hi - lo, &r, nullptr), "mnt753_check_points");
       if (r.n_bad && !total.n_bad) { total.first_bad = lo + r.first_bad; total.first_reason = r.first_reason; }
       total.n_bad += r.n_bad;
     }
@@ -1313,7 +1319,13 @@ template <int CURVE> typename HIP_B::check_report HIP_B::check_params_file(const
   }
   return rep;
 }
-template <int CURVE> typename HIP_B::check_report HIP_B::check_params(groth16_params* p) { return check_params_file(p->path.c_str()); }
+template <int CURVE> typename HIP_B::check_report HIP_B::check_params(groth16_params* p) { return check_params_file(p->path.c_str(), false); }
+template <int CURVE> typename HIP_B::check_report HIP_B::check_params(groth16_params* p, bool subgroup) { return check_params_file(p->path.c_str(), subgroup); }
+template <int CURVE> typename HIP_B::check_entry HIP_B::check_subgroup(const uint64_t* g2_affine, size_t n) {
+  mnt753_check_report r;
+  check(mnt753_check_subgroup(CURVE, MNT753_G2, g2_affine, 0, n, &r, nullptr), "mnt753_check_subgroup");
+  return {"G2", n, r.n_bad, r.first_bad, (int)r.first_reason};
+}
 
 // w, ca, cb, cc, r canonical; then the rows: ca[i] cb[i] = cc[i] on the vectors as they lie on the device, or -- cs given -- the
 // system evaluated on w once more (mnt753_r1cs_check)
@@ -1386,11 +1398,16 @@ template <int CURVE> std::vector<uint64_t> HIP_B::pairing(const uint64_t* g1_aff
   return out;
 }
 template <int CURVE> std::vector<uint8_t> HIP_B::verify(const uint64_t* vk_elements, size_t num_inputs, const uint64_t* proofs, const uint64_t* inputs, size_t n) {
+  return verify(vk_elements, num_inputs, proofs, inputs, n, false);
+}
+template <int CURVE> std::vector<uint8_t> HIP_B::verify(const uint64_t* vk_elements, size_t num_inputs, const uint64_t* proofs, const uint64_t* inputs, size_t n,
+                                                        bool check_subgroup) {
   const size_t w2 = mnt753_affine_words(CURVE, MNT753_G2);
   mnt753_vk* vk = nullptr;
   check(mnt753_vk_create(CURVE, vk_elements, vk_elements + 24, vk_elements + 24 + w2, vk_elements + 24 + 2 * w2, num_inputs, &vk), "mnt753_vk_create");
   std::vector<uint8_t> verdicts(n);
-  const int rc = mnt753_groth16_verify(vk, proofs, inputs, n, 0, verdicts.data(), nullptr);
+  const int rc = check_subgroup ? mnt753_groth16_verify_ex(vk, proofs, inputs, n, 0, MNT753_VERIFY_CHECK_SUBGROUP, verdicts.data(), nullptr)
+                                : mnt753_groth16_verify(vk, proofs, inputs, n, 0, verdicts.data(), nullptr);
   mnt753_vk_destroy(vk);
   if (rc < 0) check(rc, "mnt753_groth16_verify");
   return verdicts;

@@ -93,8 +93,43 @@ def pairing_constants(curve):
     assert w0 == (-(loop - 1) if curve == 0 else loop)
     gamma = [pow(nr, (q ** i - 1) // k, q) for i in range(k)]
     assert all(pow(g, k, q) == 1 for g in gamma)
+    psi_x, psi_y = subgroup_constants(curve, q, r, k, gamma[1])
     return {"q": q, "k": k, "loop": loop, "loop_neg": q < r, "w0_abs": abs(w0), "w0_neg": w0 < 0, "nr_inv": pow(nr, -1, q),
-            "frob": [[pow(g, j, q) for j in range(k)] for g in gamma]}
+            "frob": [[pow(g, j, q) for j in range(k)] for g in gamma], "psi_x": psi_x, "psi_y": psi_y}
+
+
+def subgroup_constants(curve, q, r, k, gamma1):
+    """gamma_1^-2 and gamma_1^-3: the constants of psi = twist^-1 o Frobenius_q o twist on the twisted curve E'(F), F = Fq2 / Fq3,
+    psi(x, y) = (x^q gamma_1^-2, y^q gamma_1^-3).  With w^2 = u = twist the untwisting map is (x, y) -> (x / w^2, y / w^3), so the
+    constants are w^(2 (1 - q)) = twist^(1 - q) and w^(3 (1 - q)) = twist^(3 (1 - q) / 2); both lie in Fq.  psi satisfies
+    X^2 - t X + q with t = q + 1 - r, and G2 is its eigenspace of the eigenvalue q = t - 1 (mod r): on G2::one() psi is the
+    multiplication by q - r = t - 1, the (signed) ate loop count.  That fixes the sign of the y constant; all three are asserted."""
+    import pyref
+    C = pyref.Curve(curve)
+    deg = k // 2
+    psi_x, psi_y = pow(gamma1, -2, q), pow(gamma1, -3, q)
+    twist = tuple(1 if j == 1 else 0 for j in range(deg))
+
+    def f_pow(x, e):
+        acc = C.f_one(x)
+        for bit in bin(e)[2:]:
+            acc = C.f_mul(acc, acc)
+            if bit == "1":
+                acc = C.f_mul(acc, x)
+        return acc
+    twist_inv = C.f_inv(twist)
+    embed = lambda c: (c,) + (0,) * (deg - 1)
+    assert f_pow(twist_inv, q - 1) == embed(psi_x)                 # twist^(1 - q), zero higher components
+    assert f_pow(twist_inv, 3 * (q - 1) // 2) == embed(psi_y)      # twist^(3 (1 - q) / 2)
+    # x^q in F: component c times gamma_1^(2 c) (the existing frob[1][2 c])
+    frob = lambda x: tuple(x[c] * pow(gamma1, 2 * c, q) % q for c in range(deg))
+    gx, gy = C.gen(2)
+    psi_g = (tuple(v * psi_x % q for v in frob(gx)), tuple(v * psi_y % q for v in frob(gy)))
+    want = C.mul(abs(q - r), (gx, gy), 2)
+    if q < r:
+        want = C.neg(want)
+    assert C.on_curve(psi_g, 2) and psi_g == want                   # psi(G2::one()) == [q - r] G2::one()
+    return psi_x, psi_y
 
 
 def emit_pairing():
@@ -114,6 +149,7 @@ def emit_pairing():
     out.append("  int w0_bits, w0_neg;")
     out.append("  uint32_t nr_inv[NL];       // 1 / NR, device form: the twist's inverse is u^(deg - 1) / NR")
     out.append("  uint32_t frob[6][6][NL];   // frob[i][j] = gamma_i^j, device form; entries with i or j >= k are zero")
+    out.append("  uint32_t psi_x[NL], psi_y[NL];   // gamma_1^-2, gamma_1^-3, device form: psi(x, y) = (x^q psi_x, y^q psi_y) on the twist (subgroup test)")
     out.append("};")
     out.append("static constexpr PairingConst PAIRC[2] = {")
     for curve in (0, 1):
@@ -127,7 +163,7 @@ def emit_pairing():
         for i in range(6):
             row = [dev(c["frob"][i][j]) if i < k and j < k else arr([0] * NL, 7) for j in range(6)]
             s += "     {" + ",\n      ".join(row) + "}" + (",\n" if i < 5 else "\n")
-        s += "    }\n  }" + ("," if curve == 0 else "")
+        s += "    },\n    %s,\n    %s\n  }" % (dev(c["psi_x"]), dev(c["psi_y"])) + ("," if curve == 0 else "")
         out.append(s)
     out.append("};")
     out.append("}  // namespace mnt753")

@@ -204,6 +204,15 @@ int mnt753_check_points(int curve, int group, const uint64_t* aff, int, size_t n
   stub_report(out, "MNT753_STUB_BAD_POINT", n, MNT753_BAD_OFF_CURVE);
   return 0;
 }
+// the subgroup test: G1 is check_points' own result; on G2 MNT753_STUB_BAD_SUBGROUP=<index> asks for one point outside the subgroup at
+// that index of every G2 set long enough to have it (MNT753_STUB_BAD_POINT, an earlier reason, wins where both name a point)
+int mnt753_check_subgroup(int curve, int group, const uint64_t* aff, int od, size_t n, mnt753_check_report* out, void* st) {
+  if (bad_cg(curve, group) || !out || (n && !aff)) return fail(MNT753_EINVAL, "check_subgroup: bad argument");
+  if (int rc = mnt753_check_points(curve, group, aff, od, n, out, st)) return rc;
+  if (group == MNT753_G1 || out->n_bad) return 0;
+  stub_report(out, "MNT753_STUB_BAD_SUBGROUP", n, MNT753_BAD_NOT_IN_SUBGROUP);
+  return 0;
+}
 int mnt753_check_scalars(int curve, const uint64_t* fr, int, size_t n, mnt753_check_report* out, void*) {
   if (curve < 0 || curve > 1 || !out || (n && !fr)) return fail(MNT753_EINVAL, "check_scalars: bad argument");
   if (!g_ndev) return fail(MNT753_ENODEV, "no device");
@@ -276,12 +285,19 @@ int mnt753_vk_accumulate(const mnt753_vk* vk, const uint64_t* inputs, size_t n, 
   for (size_t i = 0; i < 24 * n; ++i) out[i] = i;
   return 0;
 }
-int mnt753_groth16_verify(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int, uint8_t* verdicts, void*) {
-  if (!vk || (n && (!proofs || !verdicts))) return fail(MNT753_EINVAL, "groth16_verify: bad argument");
+// with MNT753_VERIFY_CHECK_SUBGROUP, MNT753_STUB_BAD_B=<index> gives that proof verdict 3
+int mnt753_groth16_verify_ex(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int, unsigned flags, uint8_t* verdicts, void*) {
+  if (!vk || (n && (!proofs || !verdicts)) || (flags & ~MNT753_VERIFY_CHECK_SUBGROUP)) return fail(MNT753_EINVAL, "groth16_verify: bad argument");
   touch_ro(proofs, n * (48 + mnt753_affine_words(vk->curve, MNT753_G2))); touch_ro(inputs, 12 * vk->num_inputs * n);
   const int reject = getenv("MNT753_STUB_REJECT") != nullptr;
-  for (size_t i = 0; i < n; ++i) verdicts[i] = reject ? 2 : 0;
-  return reject ? (int)n : 0;
+  const char* e = (flags & MNT753_VERIFY_CHECK_SUBGROUP) ? getenv("MNT753_STUB_BAD_B") : nullptr;
+  const size_t bad_b = e && *e ? strtoull(e, nullptr, 0) : n;
+  int rejected = 0;
+  for (size_t i = 0; i < n; ++i) { verdicts[i] = i == bad_b ? 3 : (reject ? 2 : 0); rejected += verdicts[i] != 0; }
+  return rejected;
+}
+int mnt753_groth16_verify(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int od, uint8_t* verdicts, void* st) {
+  return mnt753_groth16_verify_ex(vk, proofs, inputs, n, od, 0u, verdicts, st);
 }
 int mnt753_group_generator(int curve, int group, uint64_t* out) {
   if (curve < 0 || curve > 1 || (group != MNT753_G1 && group != MNT753_G2) || !out) return fail(MNT753_EINVAL, "group_generator: bad argument");
