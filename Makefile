@@ -21,8 +21,9 @@ MAIN := $(PKG)/main_hip
 
 LAZY_TEST := $(PKG)/lazy_c_test
 PAIRING_TEST := $(PKG)/pairing_wrapper_test
+HCHECK_TEST := $(PKG)/h_check_wrapper_test
 
-all: $(LIB) $(TESTLIB) $(MAIN) $(LAZY_TEST) $(PAIRING_TEST) oracle
+all: $(LIB) $(TESTLIB) $(MAIN) $(LAZY_TEST) $(PAIRING_TEST) $(HCHECK_TEST) oracle
 
 # the wrapper's expression fusion from the caller's side (tools/host_tests/lazy_c_test.cpp; run by tests/test_prover_gpu.py)
 $(LAZY_TEST): tools/host_tests/lazy_c_test.cpp $(HOST)/prover_hip_functions.cpp include/prover_hip_functions.hpp include/mnt753_hip.h $(LIB)
@@ -31,6 +32,10 @@ $(LAZY_TEST): tools/host_tests/lazy_c_test.cpp $(HOST)/prover_hip_functions.cpp 
 # B::pairing / B::verify from the caller's side (tools/host_tests/pairing_wrapper_test.cpp; run by tests/test_pairing_gpu.py)
 $(PAIRING_TEST): tools/host_tests/pairing_wrapper_test.cpp $(HOST)/prover_hip_functions.cpp include/prover_hip_functions.hpp include/mnt753_hip.h $(LIB)
 	g++ -O2 -std=c++17 -pthread -o $@ tools/host_tests/pairing_wrapper_test.cpp $(HOST)/prover_hip_functions.cpp -L$(PKG) -lmnt753_hip -Wl,-rpath,'$$ORIGIN'
+
+# B::check_H from the caller's side (tools/host_tests/h_check_wrapper_test.cpp; run by tests/test_hcheck_gpu.py)
+$(HCHECK_TEST): tools/host_tests/h_check_wrapper_test.cpp $(HOST)/prover_hip_functions.cpp include/prover_hip_functions.hpp include/mnt753_hip.h $(LIB)
+	g++ -O2 -std=c++17 -pthread -o $@ tools/host_tests/h_check_wrapper_test.cpp $(HOST)/prover_hip_functions.cpp -L$(PKG) -lmnt753_hip -Wl,-rpath,'$$ORIGIN'
 
 $(MAIN): $(HOST)/main.cpp $(HOST)/prover_hip_functions.cpp include/prover_hip_functions.hpp include/mnt753_hip.h $(LIB)
 	g++ -O2 -std=c++17 -pthread -o $@ $(HOST)/main.cpp $(HOST)/prover_hip_functions.cpp -L$(PKG) -lmnt753_hip -Wl,-rpath,'$$ORIGIN'
@@ -72,7 +77,7 @@ $(BUILD)/san/main_hip_tsan: $(SAN_SRCS) include/prover_hip_functions.hpp include
 	g++ -O1 -g -std=c++17 -pthread -fsanitize=thread -o $@ $(SAN_SRCS)
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(TESTLIB) $(MAIN) $(LAZY_TEST) $(PAIRING_TEST)
+	rm -rf $(BUILD) $(LIB) $(TESTLIB) $(MAIN) $(LAZY_TEST) $(PAIRING_TEST) $(HCHECK_TEST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean asan tsan

@@ -316,6 +316,32 @@ int mnt753_domain_lagrange_at(mnt753_domain* d, const uint64_t* host_t, uint64_t
 /* dev_out[i] = t^i, i < n: the Ht of r1cs_to_qap.tcc:155-159.  n = 0 succeeds and writes nothing. */
 int mnt753_vec_powers(int curve, const uint64_t* host_t, uint64_t* dev_out, size_t n, void* stream);   /* 1, t, ..., t^(n-1) */
 
+/* ---- reductions over Fr and the spot check of compute_H: H(t) Z(t) = A(t) B(t) - C(t) at one point -------
+ * The reducing calls return their result to HOST memory in canonical wire form and wait for `stream`; the vectors are device memory
+ * on the calling thread's current device (domain calls: on the domain's device).  Results do not depend on the launch geometry.
+ * A device keeps 340 KB of partial sums from its first reduction on; reductions on one device take turns.
+ * sum a[i] b[i], i < n; dev_a may equal dev_b.  n = 0 gives zero. */
+int mnt753_vec_dot(int curve, const uint64_t* dev_a, const uint64_t* dev_b, size_t n, uint64_t* host_out, void* stream);
+/* sum c[i] t^i, i < n; t canonical (else MNT753_EINVAL); host result as above. */
+int mnt753_poly_eval(int curve, const uint64_t* dev_coeffs, size_t n, const uint64_t* host_t, uint64_t* host_out, void* stream);
+/* the values at t of the k <= 3 polynomials of degree < m that take dev_vecs[j][i] at the domain's i-th element, every kind of
+ * domain, t anywhere (inside the domain it returns that element of each vector).  dev_u: m elements of scratch, receives L(t)
+ * (the words of mnt753_domain_lagrange_at, whose workspace and ordering rules apply). */
+int mnt753_domain_interp_at(mnt753_domain* d, const uint64_t* host_t, const uint64_t* const* dev_vecs, int k, uint64_t* dev_u,
+                            uint64_t* host_out /* k elements */, void* stream);
+typedef struct { int32_t ok, reserved; uint64_t lhs[12], rhs[12]; } mnt753_h_check_result;   /* A(t)B(t) - C(t) and Z(t)H(t) */
+/* after compute_h: host_abc = A(t) | B(t) | C(t) from mnt753_domain_interp_at BEFORE compute_h overwrote the vectors; dev_h the m + 1
+ * coefficients.  A failed identity is ok = 0 with return code 0; with probability >= 1 - 2m/r over t it fails whenever a row has
+ * ca cb != cc or a coefficient of H is wrong.  t inside the domain (Z(t) = 0, the check would say nothing about H) is MNT753_EINVAL,
+ * as in mnt753_groth16_generate; so are t >= r and a non-canonical host_abc.  An error leaves *out untouched. */
+int mnt753_h_check(mnt753_domain* d, const uint64_t* host_t, const uint64_t* host_abc, const uint64_t* dev_h, mnt753_h_check_result* out,
+                   void* stream);
+/* interp_at (k = 3) + mnt753_compute_h + mnt753_h_check.  host_t == NULL: t from getrandom, reduced below r, redrawn if inside the
+ * domain.  No workspace beyond mnt753_domain_lagrange_at's: L(t) lies in dev_h until compute_h writes there.  A refused t leaves the
+ * vectors, dev_h and *out untouched. */
+int mnt753_compute_h_checked(mnt753_domain* d, uint64_t* dev_ca, uint64_t* dev_cb, uint64_t* dev_cc, uint64_t* dev_h, const uint64_t* host_t,
+                             mnt753_h_check_result* out, void* stream);
+
 /* ---- witness-map front end (the step before the hot path) -------------------------------------------
  * The reference evaluates the constraint system on the assignment on the CPU before the prover starts
  * (libsnark/generate_parameters.cpp:44-57 writes the result into the input file as ca / cb / cc; it is the first loop of

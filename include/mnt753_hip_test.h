@@ -79,6 +79,13 @@ int mnt753_test_miller_loop(int curve, int split, const uint64_t* g1_affine, con
 int mnt753_test_g2_endomorphism(int curve, const uint64_t* g2_affine, size_t n, uint64_t* out_affine);
 int mnt753_test_g2_loop_multiple(int curve, const uint64_t* g2_affine, size_t n, uint64_t* out_affine);
 
+/* mnt753_vec_dot (op 0: a = dev_a, b = dev_b) or mnt753_poly_eval (op 1: coefficients dev_a, t = host_t, dev_b unused) with at most
+ * max_blocks blocks of 256 threads in the reducing launch (0: the device's own cap), so that a test reaches the second grid-stride trip
+ * of a thread at a small n: one block covers 256 elements of a dot and 256 * 16 coefficients of a polynomial.  Device pointers, the
+ * result on the host, as in the calls themselves. */
+int mnt753_test_reduce_capped(int curve, int op, const uint64_t* dev_a, const uint64_t* dev_b, size_t n, const uint64_t* host_t, unsigned max_blocks,
+                              uint64_t* host_out);
+
 #ifdef __cplusplus
 }
 #endif

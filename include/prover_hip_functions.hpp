@@ -21,6 +21,8 @@
 #include <cstddef>
 #include <cstdint>
 #include <memory>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 namespace mnt753_hip_detail {
@@ -101,6 +103,24 @@ public:
   // ---- extensions (not in the reference wrapper) -------------------------------------------------
   // the whole of compute_H<B> in one device-resident call (overwrites ca, cb, cc like the reference)
   static vector_Fr *compute_H_fused(evaluation_domain *domain, vector_Fr *ca, vector_Fr *cb, vector_Fr *cc);
+  // ---- the spot check of compute_H: H(t) Z(t) = A(t) B(t) - C(t) at one point t (mnt753_h_check) ----------
+  // A(t), B(t), C(t) are the values at t of the polynomials that take ca, cb, cc on the domain: they must be taken BEFORE compute_H
+  // overwrites the vectors (h_check_begin: one inner product per vector against L(t), each on the device its vector lives on), and
+  // are compared with Z(t) H(t) once the coefficients exist (h_check_finish, on h's device; it frees the state).  t: 12 words in wire
+  // form, or null for a random point from the operating system; a t inside the domain or >= r throws.  With probability >= 1 - 2m/r
+  // over t the identity fails whenever a row has ca cb != cc or a coefficient of H is wrong.
+  struct h_check_state;
+  struct h_check_result {
+    bool ok;
+    uint64_t t[12], lhs[12], rhs[12];      // the point, A(t) B(t) - C(t) and Z(t) H(t), wire form
+    std::string message() const;           // "H: H·Z = A·B − C fails at t = 0x…" (t as an integer in the Montgomery wire form's words)
+  };
+  struct h_check_failed : std::runtime_error { using std::runtime_error::runtime_error; };
+  static h_check_state *h_check_begin(evaluation_domain *domain, vector_Fr *ca, vector_Fr *cb, vector_Fr *cc, const uint64_t *t_or_null);
+  static h_check_result h_check_finish(h_check_state *state, vector_Fr *h);
+  // true: compute_H_fused runs both around its transforms, at a random t, and throws h_check_failed where the identity fails
+  // (off by default; main_hip --check-h calls begin and finish itself, around either form of compute_H)
+  static void check_H(bool on);
   // C = Ht + Lt + r Bt1 (cuda_prover_piecewise.cu:79-90: three multiexps, B::G1_scale, two B::G1_add) as ONE multi-scalar
   // multiplication over the concatenated base set H | L | B1 with the scalars coefficients_for_H | w_L | r w.  The same group
   // element, hence the same proof bytes.  read_params builds the concatenated set (and B1 / L / H as sets of their own only when

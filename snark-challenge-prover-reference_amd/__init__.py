@@ -11,7 +11,7 @@ from .api import (  # noqa: F401
     point_add, point_scale, point_to_affine, point_from_affine, vec_muleq, vec_subeq, vec_scale, copy_d2d,
     synth_points, synth_scalars, synth_expected_msm, msm_last_timing, msm_last_plan, DeviceBuffer, R1cs, read_r1cs_file, self_test,
     check_points, check_scalars, check_products, CheckReport, BAD_NONE, BAD_NONCANONICAL, BAD_OFF_CURVE, BAD_UNSATISFIED, FixedBase,
-    vec_powers, QapPlan, generate, GeneratedKey, write_r1cs_file, group_generator, compact_nonzero, scatter_rows, keygen_combine,
+    vec_powers, vec_dot, poly_eval, HCheckResult, QapPlan, generate, GeneratedKey, write_r1cs_file, group_generator, compact_nonzero, scatter_rows, keygen_combine,
     pairing, gt_words, VerificationKey, check_subgroup, BAD_NOT_IN_SUBGROUP, VERIFY_CHECK_SUBGROUP,
 )
 from . import parallel  # noqa: F401,E402

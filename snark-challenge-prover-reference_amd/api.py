@@ -58,6 +58,11 @@ class KeygenReport(C.Structure):
 KEYGEN_DENSE_G1, KEYGEN_DENSE_G2 = 1, 2
 
 
+class HCheckResult(C.Structure):
+    """mnt753_h_check_result: the verdict of H(t) Z(t) = A(t) B(t) - C(t) and its two sides in wire form"""
+    _fields_ = [("ok", C.c_int32), ("reserved", C.c_int32), ("lhs", C.c_uint64 * 12), ("rhs", C.c_uint64 * 12)]
+
+
 def lib_path():
     """The product library next to this file; MNT753_LIB names another build of it (development A/B runs: an experimental
     variant is loaded from where it was built instead of being copied over the product file)."""
@@ -137,6 +142,11 @@ def lib():
         "mnt753_domain_vanishing_at": (i, [vp, u64p, u64p]),
         "mnt753_domain_lagrange_at": (i, [vp, u64p, vp, vp]),
         "mnt753_vec_powers": (i, [i, u64p, vp, sz, vp]),
+        "mnt753_vec_dot": (i, [i, vp, vp, sz, u64p, vp]),
+        "mnt753_poly_eval": (i, [i, vp, sz, u64p, u64p, vp]),
+        "mnt753_domain_interp_at": (i, [vp, u64p, C.POINTER(vp), i, vp, u64p, vp]),
+        "mnt753_h_check": (i, [vp, u64p, u64p, vp, C.POINTER(HCheckResult), vp]),
+        "mnt753_compute_h_checked": (i, [vp, vp, vp, vp, vp, u64p, C.POINTER(HCheckResult), vp]),
         "mnt753_r1cs_qap_plan": (i, [vp, C.POINTER(QapPlan)]),
         "mnt753_r1cs_qap_at": (i, [vp, vp, u64p, vp, vp, vp, vp, u64p, vp]),
         "mnt753_synth_scalars": (i, [i, C.c_uint64, sz, u64p]),
@@ -218,6 +228,7 @@ def test_lib():
         "mnt753_test_miller_loop": (i, [i, i, u64p, u64p, sz, u64p]),
         "mnt753_test_g2_endomorphism": (i, [i, u64p, sz, u64p]),
         "mnt753_test_g2_loop_multiple": (i, [i, u64p, sz, u64p]),
+        "mnt753_test_reduce_capped": (i, [i, i, C.c_void_p, C.c_void_p, sz, u64p, C.c_uint, u64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -489,6 +500,47 @@ class Domain:
         finally:
             buf.close()
 
+    def interp_at(self, t, vecs, u_ptr=None, stream=None):
+        """The values at t of the polynomials (1 to 3 of them, degree < m) that take vecs[j][i] at the domain's i-th element
+        (mnt753_domain_interp_at): vecs are device addresses of m elements each, the result a numpy array [len(vecs), 12].  u_ptr: m
+        elements of device scratch that receive L(t); without it the call brings its own."""
+        k, pk = _fr_elem(t)
+        st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+        arr = (C.c_void_p * len(vecs))(*[int(v) for v in vecs])
+        out = np.zeros((len(vecs), 12), dtype=np.uint64)
+        buf = DeviceBuffer(96 * self.m) if u_ptr is None else None
+        try:
+            u = buf.ptr if buf is not None else C.c_void_p(int(u_ptr))
+            _check(lib().mnt753_domain_interp_at(self._h, pk, arr, len(vecs), u, out.ctypes.data_as(C.POINTER(C.c_uint64)), st),
+                   "mnt753_domain_interp_at")
+        finally:
+            if buf is not None:
+                buf.close()
+        return out
+
+    def h_check(self, t, abc, h, stream=None):
+        """After compute_h: (ok, lhs, rhs) of H(t) Z(t) = A(t) B(t) - C(t) (mnt753_h_check).  abc: A(t) | B(t) | C(t) as interp_at
+        returned them BEFORE compute_h overwrote the vectors; h: the device address of the m + 1 coefficients."""
+        k, pk = _fr_elem(t)
+        st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+        a = np.ascontiguousarray(abc, dtype=np.uint64).reshape(-1)
+        assert a.size == 36
+        res = HCheckResult()
+        _check(lib().mnt753_h_check(self._h, pk, a.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(int(h)), C.byref(res), st), "mnt753_h_check")
+        return bool(res.ok), np.array(res.lhs, dtype=np.uint64), np.array(res.rhs, dtype=np.uint64)
+
+    def compute_h_checked(self, ca, cb, cc, h, t=None, stream=None):
+        """compute_h with the spot check around it (mnt753_compute_h_checked): (ok, lhs, rhs).  t=None: a random point from the
+        operating system."""
+        st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+        pk = None
+        if t is not None:
+            k, pk = _fr_elem(t)
+        res = HCheckResult()
+        _check(lib().mnt753_compute_h_checked(self._h, C.c_void_p(int(ca)), C.c_void_p(int(cb)), C.c_void_p(int(cc)), C.c_void_p(int(h)),
+                                              pk, C.byref(res), st), "mnt753_compute_h_checked")
+        return bool(res.ok), np.array(res.lhs, dtype=np.uint64), np.array(res.rhs, dtype=np.uint64)
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib().mnt753_domain_free(self._h)
@@ -522,6 +574,24 @@ def vec_powers(curve, t, n, out_ptr=None, stream=None):
         return buf.to_numpy().reshape(-1, 12)[:int(n)]
     finally:
         buf.close()
+
+
+def vec_dot(curve, a_ptr, b_ptr, n, stream=None):
+    """sum a[i] b[i] over n elements of Fr on the device (mnt753_vec_dot): 12 uint64 in wire form; a_ptr may equal b_ptr."""
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    out = np.zeros(12, dtype=np.uint64)
+    _check(lib().mnt753_vec_dot(curve, C.c_void_p(int(a_ptr)), C.c_void_p(int(b_ptr)), int(n), out.ctypes.data_as(C.POINTER(C.c_uint64)), st),
+           "mnt753_vec_dot")
+    return out
+
+
+def poly_eval(curve, coeffs_ptr, n, t, stream=None):
+    """sum c[i] t^i over n coefficients on the device (mnt753_poly_eval): 12 uint64 in wire form."""
+    k, pk = _fr_elem(t)
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    out = np.zeros(12, dtype=np.uint64)
+    _check(lib().mnt753_poly_eval(curve, C.c_void_p(int(coeffs_ptr)), int(n), pk, out.ctypes.data_as(C.POINTER(C.c_uint64)), st), "mnt753_poly_eval")
+    return out
 
 
 def vec_muleq(curve, a_ptr, b_ptr, n, stream=None):

@@ -4,13 +4,17 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <new>
 #include <vector>
+#include <sys/random.h>
 
 #include "common_host.hpp"
 #include "host_field.hpp"
 #include "ntt_kernels.hip.h"
 #include "qap_kernels.hip.h"
+#include "reduce_kernels.hip.h"
+#include "reduce_api.hpp"
 
 using namespace mnt753;
 using namespace mnt753::host;
@@ -881,6 +885,214 @@ int mnt753_vec_powers(int curve, const uint64_t* host_t, uint64_t* dev_out, size
   else hipLaunchKernelGGL((k_vec_powers<MOD_B>), dim3(g), dim3(256), 0, (hipStream_t)stream, out, t, n);
   HIP_TRY(hipGetLastError());
   return 0;
+}
+
+}  // extern "C"
+
+// ---- reductions over Fr and the spot check of compute_H (reduce_kernels.hip.h) -------------------------------
+namespace {
+
+// The partial sums of a launch and its results, one buffer per device for the life of the process (340 KB).  A reduction holds
+// the device's mutex from its first launch until its result is on the host: every one of these calls waits for its stream anyway.
+struct RedScratch {
+  std::mutex mu;
+  uint32_t* p = nullptr;      // RED_MAX_BLOCKS * 3 partials, then 3 results in wire form
+  unsigned cap = 0;           // blocks per launch on this device
+};
+constexpr int RED_MAX_DEVICES = 64;
+int current_device_ordinal() {      // HIP's current device: the one the launches below go to (OnDevice, or the caller's own)
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; }
+  return dev;
+}
+RedScratch g_red[RED_MAX_DEVICES];
+constexpr size_t RED_PARTIAL_WORDS = (size_t)RED_MAX_BLOCKS * 3 * FPS_WORDS;
+
+int red_scratch(int dev, RedScratch** out) {      // the caller is on device `dev`
+  if (dev < 0 || dev >= RED_MAX_DEVICES) return set_error(MNT753_EINVAL, "reduction: device ordinal out of range");
+  RedScratch* s = &g_red[dev];
+  std::lock_guard<std::mutex> lock(s->mu);
+  if (!s->p) {
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const unsigned cap = (unsigned)(cus > 0 ? cus : 1) * RED_BLOCKS_PER_CU;
+    uint32_t* p = nullptr;
+    if (hipMalloc(&p, (RED_PARTIAL_WORDS + 3 * 24) * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      return set_error(MNT753_ENOMEM, "reduction: device allocation failed");
+    }
+    s->cap = cap < RED_MAX_BLOCKS ? cap : RED_MAX_BLOCKS;
+    s->p = p;
+  }
+  *out = s;
+  return 0;
+}
+
+// k (1 or 3) inner products over n > 0 elements against u, results to the host; on the current device, which owns the vectors.
+// max_blocks: 0 for the device's own cap, else a smaller one (the test hook)
+template <int M>
+int dot_t(const uint32_t* const* vecs, int k, const uint32_t* u, size_t n, uint64_t* host_out, unsigned max_blocks, hipStream_t st) {
+  RedScratch* s = nullptr;
+  if (int rc = red_scratch(current_device_ordinal(), &s)) return rc;
+  std::lock_guard<std::mutex> lock(s->mu);
+  unsigned cap = s->cap;
+  if (max_blocks && max_blocks < cap) cap = max_blocks;
+  const size_t want = (n + RED_BLOCK - 1) / RED_BLOCK;
+  const unsigned nb = (unsigned)(want < cap ? want : cap);
+  uint32_t* res = s->p + RED_PARTIAL_WORDS;
+  DotVecs v{{vecs[0], k == 3 ? vecs[1] : vecs[0], k == 3 ? vecs[2] : vecs[0]}};
+  if (k == 3) hipLaunchKernelGGL((k_vec_dot<M, 3>), dim3(nb), dim3(RED_BLOCK), 0, st, v, u, n, s->p);
+  else hipLaunchKernelGGL((k_vec_dot<M, 1>), dim3(nb), dim3(RED_BLOCK), 0, st, v, u, n, s->p);
+  hipLaunchKernelGGL((k_red_fold<M>), dim3(1), dim3(RED_BLOCK), 0, st, s->p, nb, k, 1, res);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host_out, res, (size_t)k * 96, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+
+template <int M>
+int poly_t(const uint32_t* c, size_t n, const uint64_t* host_t, uint64_t* host_out, unsigned max_blocks, hipStream_t st) {
+  RedScratch* s = nullptr;
+  if (int rc = red_scratch(current_device_ordinal(), &s)) return rc;
+  std::lock_guard<std::mutex> lock(s->mu);
+  unsigned cap = s->cap;
+  if (max_blocks && max_blocks < cap) cap = max_blocks;
+  const size_t runs = (n + POLY_RUN - 1) / POLY_RUN;
+  const size_t want = (runs + RED_BLOCK - 1) / RED_BLOCK;
+  const unsigned nb = (unsigned)(want < cap ? want : cap);
+  uint32_t* res = s->p + RED_PARTIAL_WORDS;
+  WireElem t;
+  memcpy(t.w, host_t, 96);
+  hipLaunchKernelGGL((k_poly_eval<M>), dim3(nb), dim3(RED_BLOCK), 0, st, c, n, t, s->p);
+  hipLaunchKernelGGL((k_red_fold<M>), dim3(1), dim3(RED_BLOCK), 0, st, s->p, nb, 1, 0, res);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host_out, res, 96, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+
+int vec_dot_impl(int curve, const uint64_t* dev_a, const uint64_t* dev_b, size_t n, uint64_t* host_out, unsigned max_blocks, void* stream) {
+  if (curve < 0 || curve > 1 || !host_out || (n && (!dev_a || !dev_b))) return set_error(MNT753_EINVAL, "vec_dot: bad argument");
+  if (int rc = require_device()) return rc;
+  if (n == 0) {
+    memset(host_out, 0, 96);
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+  }
+  const uint32_t* a = reinterpret_cast<const uint32_t*>(dev_a);
+  const uint32_t* b = reinterpret_cast<const uint32_t*>(dev_b);
+  return curve == MNT753_CURVE_MNT4753 ? dot_t<MOD_A>(&a, 1, b, n, host_out, max_blocks, (hipStream_t)stream)
+                                       : dot_t<MOD_B>(&a, 1, b, n, host_out, max_blocks, (hipStream_t)stream);
+}
+
+int poly_eval_impl(int curve, const uint64_t* dev_coeffs, size_t n, const uint64_t* host_t, uint64_t* host_out, unsigned max_blocks, void* stream) {
+  if (curve < 0 || curve > 1 || !host_t || !host_out || (n && !dev_coeffs)) return set_error(MNT753_EINVAL, "poly_eval: bad argument");
+  if (!fr_canonical(curve == MNT753_CURVE_MNT4753 ? MOD_A : MOD_B, host_t)) return set_error(MNT753_EINVAL, "poly_eval: t is not a canonical element of Fr");
+  if (int rc = require_device()) return rc;
+  if (n == 0) {
+    memset(host_out, 0, 96);
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+  }
+  const uint32_t* c = reinterpret_cast<const uint32_t*>(dev_coeffs);
+  return curve == MNT753_CURVE_MNT4753 ? poly_t<MOD_A>(c, n, host_t, host_out, max_blocks, (hipStream_t)stream)
+                                       : poly_t<MOD_B>(c, n, host_t, host_out, max_blocks, (hipStream_t)stream);
+}
+
+template <int M>
+bool vanishes_t(const mnt753_domain* d, const uint64_t* host_t) { return vanishing_t<M>(d, HFp<M>::from_words(host_t)).is_zero(); }
+bool vanishes(const mnt753_domain* d, const uint64_t* host_t) { return d->frm == MOD_A ? vanishes_t<MOD_A>(d, host_t) : vanishes_t<MOD_B>(d, host_t); }
+
+// lhs = A B - C, rhs = Z H on the host
+template <int M>
+void h_verdict_t(const mnt753_domain* d, const uint64_t* host_t, const uint64_t* abc, const uint64_t* ht, mnt753_h_check_result* out) {
+  typedef HFp<M> Fr;
+  const Fr lhs = Fr::from_words(abc) * Fr::from_words(abc + 12) - Fr::from_words(abc + 24);
+  const Fr rhs = vanishing_t<M>(d, Fr::from_words(host_t)) * Fr::from_words(ht);
+  memcpy(out->lhs, lhs.l, 96);
+  memcpy(out->rhs, rhs.l, 96);
+  out->ok = lhs == rhs ? 1 : 0;
+  out->reserved = 0;
+}
+
+}  // namespace
+
+namespace mnt753 {
+int vec_dot_capped(int curve, const uint64_t* dev_a, const uint64_t* dev_b, size_t n, uint64_t* host_out, unsigned max_blocks, void* stream) {
+  return vec_dot_impl(curve, dev_a, dev_b, n, host_out, max_blocks, stream);
+}
+int poly_eval_capped(int curve, const uint64_t* dev_coeffs, size_t n, const uint64_t* host_t, uint64_t* host_out, unsigned max_blocks, void* stream) {
+  return poly_eval_impl(curve, dev_coeffs, n, host_t, host_out, max_blocks, stream);
+}
+}  // namespace mnt753
+
+extern "C" {
+
+int mnt753_vec_dot(int curve, const uint64_t* dev_a, const uint64_t* dev_b, size_t n, uint64_t* host_out, void* stream) {
+  return vec_dot_impl(curve, dev_a, dev_b, n, host_out, 0, stream);
+}
+
+int mnt753_poly_eval(int curve, const uint64_t* dev_coeffs, size_t n, const uint64_t* host_t, uint64_t* host_out, void* stream) {
+  return poly_eval_impl(curve, dev_coeffs, n, host_t, host_out, 0, stream);
+}
+
+int mnt753_domain_interp_at(mnt753_domain* d, const uint64_t* host_t, const uint64_t* const* dev_vecs, int k, uint64_t* dev_u, uint64_t* host_out, void* stream) {
+  if (!d || !host_t || !dev_vecs || k < 1 || k > 3 || !dev_u || !host_out) return set_error(MNT753_EINVAL, "domain_interp_at: bad argument");
+  for (int j = 0; j < k; ++j)
+    if (!dev_vecs[j]) return set_error(MNT753_EINVAL, "domain_interp_at: null vector");
+  if (!fr_canonical(d->frm, host_t)) return set_error(MNT753_EINVAL, "domain_interp_at: t is not a canonical element of Fr");
+  if (int rc = mnt753_domain_lagrange_at(d, host_t, dev_u, stream)) return rc;      // takes and releases the domain's work buffer
+  OnDevice on(d->device);
+  const uint32_t* u = reinterpret_cast<const uint32_t*>(dev_u);
+  const uint32_t* v[3];
+  for (int j = 0; j < k; ++j) v[j] = reinterpret_cast<const uint32_t*>(dev_vecs[j]);
+  const hipStream_t st = (hipStream_t)stream;
+  if (k == 3) return d->frm == MOD_A ? dot_t<MOD_A>(v, 3, u, d->m, host_out, 0, st) : dot_t<MOD_B>(v, 3, u, d->m, host_out, 0, st);
+  for (int j = 0; j < k; ++j)
+    if (int rc = d->frm == MOD_A ? dot_t<MOD_A>(v + j, 1, u, d->m, host_out + 12 * j, 0, st) : dot_t<MOD_B>(v + j, 1, u, d->m, host_out + 12 * j, 0, st)) return rc;
+  return 0;
+}
+
+int mnt753_h_check(mnt753_domain* d, const uint64_t* host_t, const uint64_t* host_abc, const uint64_t* dev_h, mnt753_h_check_result* out, void* stream) {
+  if (!d || !host_t || !host_abc || !dev_h || !out) return set_error(MNT753_EINVAL, "h_check: null argument");
+  if (!fr_canonical(d->frm, host_t)) return set_error(MNT753_EINVAL, "h_check: t is not a canonical element of Fr");
+  for (int j = 0; j < 3; ++j)
+    if (!fr_canonical(d->frm, host_abc + 12 * j)) return set_error(MNT753_EINVAL, "h_check: A(t), B(t), C(t) must be canonical elements of Fr");
+  if (vanishes(d, host_t)) return set_error(MNT753_EINVAL, "h_check: t is an element of the domain (Z(t) = 0: the identity would say nothing about H)");
+  if (int rc = require_device()) return rc;
+  OnDevice on(d->device);
+  uint64_t ht[12];
+  const uint32_t* h = reinterpret_cast<const uint32_t*>(dev_h);
+  if (int rc = d->frm == MOD_A ? poly_t<MOD_A>(h, d->m + 1, host_t, ht, 0, (hipStream_t)stream) : poly_t<MOD_B>(h, d->m + 1, host_t, ht, 0, (hipStream_t)stream)) return rc;
+  if (d->frm == MOD_A) h_verdict_t<MOD_A>(d, host_t, host_abc, ht, out);
+  else h_verdict_t<MOD_B>(d, host_t, host_abc, ht, out);
+  return 0;
+}
+
+int mnt753_compute_h_checked(mnt753_domain* d, uint64_t* dev_ca, uint64_t* dev_cb, uint64_t* dev_cc, uint64_t* dev_h, const uint64_t* host_t,
+                             mnt753_h_check_result* out, void* stream) {
+  if (!d || !dev_ca || !dev_cb || !dev_cc || !dev_h || !out) return set_error(MNT753_EINVAL, "compute_h_checked: null argument");
+  uint64_t t[12];
+  if (host_t) {
+    if (!fr_canonical(d->frm, host_t)) return set_error(MNT753_EINVAL, "compute_h_checked: t is not a canonical element of Fr");
+    if (vanishes(d, host_t)) return set_error(MNT753_EINVAL, "compute_h_checked: t is an element of the domain (Z(t) = 0: the identity would say nothing about H)");
+    memcpy(t, host_t, 96);
+  }
+  if (int rc = require_device()) return rc;
+  if (!host_t) {
+    // 753 random bits, redrawn until they are below r (more than half of the draws are) and outside the domain
+    for (int tries = 0;; ++tries) {
+      if (tries == 256 || getrandom(t, sizeof t, 0) != (ssize_t)sizeof t) return set_error(MNT753_EINVAL, "compute_h_checked: no random t from getrandom");
+      t[11] &= ((uint64_t)1 << (753 - 64 * 11)) - 1;
+      if (fr_canonical(d->frm, t) && !vanishes(d, t)) break;
+    }
+  }
+  // L(t) goes into dev_h, which compute_h writes only afterwards
+  const uint64_t* vecs[3] = {dev_ca, dev_cb, dev_cc};
+  uint64_t abc[36];
+  if (int rc = mnt753_domain_interp_at(d, t, vecs, 3, dev_h, abc, stream)) return rc;
+  if (int rc = mnt753_compute_h(d, dev_ca, dev_cb, dev_cc, dev_h, stream)) return rc;
+  return mnt753_h_check(d, t, abc, dev_h, out, stream);
 }
 
 }  // extern "C"

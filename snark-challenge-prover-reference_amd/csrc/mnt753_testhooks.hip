@@ -13,6 +13,7 @@
 #include "../../include/mnt753_hip_test.h"
 #include "msm_kernels.hip.h"
 #include "field_raw_ops.hip.h"
+#include "reduce_api.hpp"
 
 using namespace mnt753;
 
@@ -434,4 +435,12 @@ extern "C" int mnt753_test_point_op(int curve, int group, int split, int op, con
   }
   if (group == MNT753_G1) return run_point_op<Mnt6G1>(op, p_proj, q_proj, n, out_proj);
   return split ? run_point_op<Mnt6G2S>(op, p_proj, q_proj, n, out_proj) : run_point_op<Mnt6G2>(op, p_proj, q_proj, n, out_proj);
+}
+
+// ---- the reductions of csrc/reduce_kernels.hip.h under a cap on the grid ----------------------------------------------------------
+extern "C" int mnt753_test_reduce_capped(int curve, int op, const uint64_t* dev_a, const uint64_t* dev_b, size_t n, const uint64_t* host_t,
+                                         unsigned max_blocks, uint64_t* host_out) {
+  if (op == 0) return vec_dot_capped(curve, dev_a, dev_b, n, host_out, max_blocks, nullptr);
+  if (op == 1) return poly_eval_capped(curve, dev_a, n, host_t, host_out, max_blocks, nullptr);
+  return set_error(MNT753_EINVAL, "test_reduce_capped: unknown op");
 }

@@ -7,8 +7,10 @@
 // ./main_hip <curve> check <params> [<input>] | check-r1cs <params> <r1cs> <witness>      (validation only; exit code 3 = malformed input)
 //            check --subgroup: B2 must also lie in the order-r subgroup of the twist; verify --check-subgroup: the key's G2 elements and every B
 //            --validate on compute / compute-r1cs / complete: the same checks before proving; a failing job writes nothing
+//            --check-h [--check-h-t <file>] on compute / compute-r1cs (or MNT753_CHECK_H=1): H(t) Z(t) = A(t) B(t) - C(t) at one point after
+//            every compute_H; a failing job writes nothing
 //            --mixed-radix on compute / compute-r1cs / complete (or MNT753_MIXED_RADIX=1): MNT6753 domains of 2^a 5^b elements, up to 819200
-// Exit codes: 0 success, 1 device / I/O / self-test failure, 2 usage, 3 an input failed validation.
+// Exit codes: 0 success, 1 device / I/O / self-test failure, 2 usage, 3 an input failed validation (or its H failed --check-h).
 //
 // The prover driver, same command line as the reference binaries (libsnark/main.cpp:274-293,
 // cuda_prover_piecewise.cu:100-120).  compute_H<B> and run_prover<B> keep the reference's shape -- they are
@@ -61,6 +63,14 @@ static bool g_validate = false;
 // (B::allow_mixed_radix); without it such a d + 1 ends with the library's message, as before
 static bool g_mixed_radix = false;
 struct validation_failed : std::runtime_error { using std::runtime_error::runtime_error; };
+// --check-h (or MNT753_CHECK_H=1): every job's quotient polynomial is checked against its ca, cb, cc at one point t before anything is
+// written, H(t) Z(t) = A(t) B(t) - C(t) (B::h_check_begin / B::h_check_finish around compute_H, fused or not, sharded or not).  A
+// random t per job, or the 96-byte wire element of --check-h-t <file> for a reproducible run.  A failing job writes no output file
+// and the process exits 3, as with --validate; unlike --validate the check also covers compute_H itself.
+static bool g_check_h = false;
+static bool g_check_h_t_given = false;
+static uint64_t g_check_h_t[12];
+static std::string g_h_failure;    // the message of the job in flight, empty while its H stands
 
 // one line per set: "A: 1048577 points ok" / "H: 3 bad, first at 524288: off curve" / "constraint 17 of 30 is not satisfied"
 template <typename B>
@@ -86,8 +96,19 @@ static void ck(int rc, const char* what) { if (rc) throw std::runtime_error(std:
 template <typename B>
 typename B::vector_Fr* compute_H(size_t d, typename B::vector_Fr* ca, typename B::vector_Fr* cb, typename B::vector_Fr* cc) {
   auto domain = B::get_evaluation_domain(d + 1);
+  // A(t), B(t), C(t) before the transforms overwrite the vectors; the verdict once the coefficients exist.  A failed identity is
+  // recorded, not thrown: the job runs to its end like any other (every buffer is released on the one path) and writes nothing.
+  typename B::h_check_state* checking = g_check_h ? B::h_check_begin(domain, ca, cb, cc, g_check_h_t_given ? g_check_h_t : nullptr) : nullptr;
+  auto verdict = [&](typename B::vector_Fr* h) {
+    if (!checking) return;
+    const auto tv = clk::now();
+    const auto res = B::h_check_finish(checking, h);
+    if (!res.ok) g_h_failure = res.message();
+    if (!g_quiet) printf("check H: %s (%.4fs behind compute_H)\n", res.ok ? "H Z = A B - C holds" : "FAILED", secs(tv, clk::now()));
+  };
   if (g_fused_h) {
     auto H_res = B::compute_H_fused(domain, ca, cb, cc);
+    verdict(H_res);
     B::delete_evaluation_domain(domain);
     return H_res;
   }
@@ -105,6 +126,7 @@ typename B::vector_Fr* compute_H(size_t d, typename B::vector_Fr* ca, typename B
   B::domain_icosetFFT(domain, H_tmp);
   typename B::vector_Fr* H_res = B::vector_Fr_zeros(m + 1);
   B::vector_Fr_copy_into(H_tmp, H_res, m);
+  verdict(H_res);
   B::delete_evaluation_domain(domain);
   return H_res;
 }
@@ -119,6 +141,7 @@ void prove_one(typename B::groth16_params* params, const char* input_path, const
   auto t_main = clk::now();
   // compute-r1cs: the input file holds w and r only; ca / cb / cc come from the constraint system, evaluated on the device
   auto input = cs ? B::read_witness(input_path, params, cs) : B::read_input(input_path, params);
+  g_h_failure.clear();
   if (g_validate) {
     // before anything is enqueued on these vectors (compute_H overwrites ca, cb, cc); waits for the input's loaders
     const auto tv = clk::now();
@@ -195,9 +218,10 @@ void prove_one(typename B::groth16_params* params, const char* input_path, const
     B::delete_G1(scaled_Bt1); B::delete_G1(Lt1_plus_scaled_Bt1);
     B::delete_vector_G1(pB1); B::delete_vector_G1(pH); B::delete_vector_G1(pL);
   }
-  B::groth16_output_write(evaluation_At, evaluation_Bt2, C, output_path);
+  const std::string h_failure = g_h_failure;
+  if (h_failure.empty()) B::groth16_output_write(evaluation_At, evaluation_Bt2, C, output_path);
   auto t_out = clk::now();
-  if (!g_quiet) {
+  if (!g_quiet && h_failure.empty()) {
     printf("G2 MSM enqueued + compute_H (input streaming in): %.3fs\nremaining MSM time: %.3fs\nC = Ht + Lt + r*Bt1: %.3fs%s\ngpu: %.4fs\nstore: %.3fs\n", secs(t_in, t_h), secs(t_h, t_msm),
            secs(t_msm, t_c), g_fused_c ? " (one MSM over H | L | B1)" : "", secs(t_in, t_c), secs(t_c, t_out));
     printf("input file on the device after: %.3fs (background loader)\n", B::input_load_seconds(input));
@@ -211,6 +235,7 @@ void prove_one(typename B::groth16_params* params, const char* input_path, const
   B::delete_vector_G1(pA); B::delete_vector_G2(pB2);
   B::delete_field(r);   // (the reference's wrapper has no delete_field and its driver leaks the element)
   B::delete_groth16_input(input);
+  if (!h_failure.empty()) throw validation_failed(h_failure);
 }
 
 // --peer-bench: what DESIGN.md section 5 ASSUMES (2.0 ms for 100 MB over one xGMI link), measured on the box the prover runs on: the
@@ -807,8 +832,11 @@ int main(int argc, char** argv) {
   }
   if (const char* e = getenv("MNT753_VALIDATE")) g_validate = atoi(e) != 0;
   if (const char* e = getenv("MNT753_MIXED_RADIX")) g_mixed_radix = atoi(e) != 0;
+  if (const char* e = getenv("MNT753_CHECK_H")) g_check_h = atoi(e) != 0;
   if (argc < 6) {
-    fprintf(stderr, "usage: %s MNT4753|MNT6753 compute <params> <input> <output> [<input2> <output2> ...] [--repeat N] [--serve] [--gpus N] [--tables | --one-shot] [--unfused-h] [--unfused-c] [--ref-order] [--fold rccl|host] [--validate] [--mixed-radix] [--quiet]\n"
+    fprintf(stderr, "usage: %s MNT4753|MNT6753 compute <params> <input> <output> [<input2> <output2> ...] [--repeat N] [--serve] [--gpus N] [--tables | --one-shot] [--unfused-h] [--unfused-c] [--ref-order] [--fold rccl|host] [--validate] [--check-h] [--check-h-t <file>] [--mixed-radix] [--quiet]\n"
+                    "  --check-h: H(t) Z(t) = A(t) B(t) - C(t) at a random t after every compute_H (also compute-r1cs); a failing job writes nothing, exit code 3\n"
+                    "  --check-h-t <file>: the point t, one 96-byte element of Fr in wire form, for a reproducible run (implies --check-h)\n"
                     "  further (input, output) pairs and --repeat prove against the parameters that are already resident on the GPU\n"
                     "       %s MNT4753|MNT6753 qap-at <r1cs> <t_file> <output> [--mixed-radix]\n", argv[0], argv[0]);
     return 2;
@@ -824,6 +852,14 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[i], "--repeat") && i + 1 < argc) { repeat = atoi(argv[++i]); continue; }
     if (!strcmp(argv[i], "--gpus") && i + 1 < argc) { g_gpus = atoi(argv[++i]); continue; }
     if (!strcmp(argv[i], "--fold") && i + 1 < argc) { g_fold_rccl = !strcmp(argv[++i], "rccl") ? 1 : 0; continue; }
+    if (!strcmp(argv[i], "--check-h-t") && i + 1 < argc) {
+      FILE* f = fopen(argv[++i], "rb");
+      const bool ok = f && fread(g_check_h_t, 1, 96, f) == 96 && fgetc(f) == EOF;
+      if (f) fclose(f);
+      if (!ok) { fprintf(stderr, "main_hip: --check-h-t %s: not a file of one 96-byte element\n", argv[i]); return 2; }
+      g_check_h = g_check_h_t_given = true;
+      continue;
+    }
     if (argv[i][0] != '-' && i + 1 < argc && argv[i + 1][0] != '-') { jobs.emplace_back(argv[i], argv[i + 1]); ++i; continue; }
     if (!strcmp(argv[i], "--fused-h")) g_fused_h = true;
     else if (!strcmp(argv[i], "--unfused-h")) g_fused_h = false;
@@ -840,6 +876,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--tables")) g_one_shot = 0;      // build the window tables even for a single proof
     else if (!strcmp(argv[i], "--one-shot")) g_one_shot = 1;    // no window tables, no warm-up MSM, whatever the job list
     else if (!strcmp(argv[i], "--validate")) g_validate = true;
+    else if (!strcmp(argv[i], "--check-h")) g_check_h = true;
     else if (!strcmp(argv[i], "--mixed-radix")) g_mixed_radix = true;
     else {
       // an option this prover does not have (or one that lost its argument), or an input without its output: refuse, do not guess

@@ -3,6 +3,7 @@
 // here every vector lives in HBM and every heavy call is a HIP kernel launch.
 #include "../../include/prover_hip_functions.hpp"
 
+#include <sys/random.h>
 #include <sys/stat.h>
 
 #include <condition_variable>
@@ -139,6 +140,8 @@ static bool one_shot_mode() {
 }
 // B::allow_mixed_radix(true): get_evaluation_domain passes MNT753_DOMAIN_ALLOW_MIXED (the library takes it per call and keeps no switch)
 static unsigned g_domain_flags = 0;
+// B::check_H(true): compute_H_fused checks H(t) Z(t) = A(t) B(t) - C(t) at a random t around its transforms
+static bool g_check_h = false;
 // contiguous slice g of n elements over n_dev devices (multiexp.tcc:417-431: one = n / chunks, the last slice takes the remainder)
 static void slice_bounds(size_t n, int n_dev, int g, size_t* lo, size_t* hi) {
   const size_t one = n / (size_t)n_dev;
@@ -1216,9 +1219,20 @@ template <int CURVE> typename HIP_B::vector_Fr* HIP_B::compute_H_fused(evaluatio
   std::shared_ptr<DeviceBuffer> h;
   { DeviceScope on(da); h = std::make_shared<DeviceBuffer>(96 * (m + 1)); }
   vector_Fr* out = new vector_Fr{h, m + 1, 0, nullptr, nullptr, nullptr};
+  h_check_state* checking = nullptr;
+  // B::check_H: A(t), B(t), C(t) before the transforms overwrite the vectors, the verdict behind them
+  auto verdict = [&]() {
+    if (!checking) return;
+    h_check_state* st = checking;
+    checking = nullptr;
+    const h_check_result res = h_check_finish(st, out);
+    if (!res.ok) throw h_check_failed(res.message());
+  };
   try {
+    if (g_check_h) checking = h_check_begin(domain, ca, cb, cc, nullptr);
     if (da == db && da == dc) {
       check(mnt753_compute_h(domain_on<CURVE>(domain, da), ca->ptr(), cb->ptr(), cc->ptr(), reinterpret_cast<uint64_t*>(h->ptr), nullptr), "mnt753_compute_h");
+      verdict();
       return out;
     }
     // the chains of the other devices first: device da is the one the rest of the proof waits for
@@ -1233,7 +1247,69 @@ template <int CURVE> typename HIP_B::vector_Fr* HIP_B::compute_H_fused(evaluatio
     check(mnt753_compute_h_finish(domain_on<CURVE>(domain, da), ca->ptr(), bp, cp, reinterpret_cast<uint64_t*>(h->ptr), nullptr), "mnt753_compute_h_finish");
     keep_alive(out->keep, keep);
     if (const char* e = getenv("MNT753_TRACE")) { if (atoi(e)) fprintf(stderr, "mnt753: compute_H over devices %d / %d / %d (chains where ca / cb / cc live, finish on %d)\n", da, db, dc, da); }
-  } catch (...) { delete out; throw; }
+    verdict();
+  } catch (...) { delete checking; delete out; throw; }
+  return out;
+}
+
+// ---- the spot check of compute_H (include/prover_hip_functions.hpp) ---------------------------------------------------------------------
+template <int CURVE> struct mnt753_hip_impl<CURVE>::h_check_state {
+  evaluation_domain* domain;
+  uint64_t t[12], abc[36];
+};
+template <int CURVE> void HIP_B::check_H(bool on) { g_check_h = on; }
+template <int CURVE> std::string HIP_B::h_check_result::message() const {
+  std::string hex;
+  char word[17];
+  for (int i = 11; i >= 0; --i) { snprintf(word, sizeof word, "%016llx", (unsigned long long)t[i]); hex += word; }
+  const size_t nz = hex.find_first_not_of('0');
+  return "H: H\xc2\xb7Z = A\xc2\xb7" "B \xe2\x88\x92 C fails at t = 0x" + (nz == std::string::npos ? std::string("0") : hex.substr(nz));
+}
+template <int CURVE> typename HIP_B::h_check_state* HIP_B::h_check_begin(evaluation_domain* domain, vector_Fr* ca, vector_Fr* cb, vector_Fr* cc,
+                                                                         const uint64_t* t_or_null) {
+  std::unique_ptr<h_check_state> st(new h_check_state);
+  st->domain = domain;
+  mnt753_domain* d0 = domain->data->h;
+  uint64_t zt[12];
+  auto zero = [](const uint64_t* w) { uint64_t o = 0; for (int i = 0; i < 12; ++i) o |= w[i]; return o == 0; };
+  if (t_or_null) {
+    memcpy(st->t, t_or_null, 96);
+    check(mnt753_domain_vanishing_at(d0, st->t, zt), "h_check_begin: t");
+    if (zero(zt)) throw std::runtime_error("h_check_begin: t is an element of the domain (Z(t) = 0: the identity would say nothing about H)");
+  } else {
+    // 753 random bits, redrawn until they are below r (more than half of the draws are) and outside the domain
+    for (int tries = 0;; ++tries) {
+      if (tries == 256 || getrandom(st->t, 96, 0) != 96) throw std::runtime_error("h_check_begin: no random t from getrandom");
+      st->t[11] &= ((uint64_t)1 << (753 - 64 * 11)) - 1;
+      if (mnt753_domain_vanishing_at(d0, st->t, zt) == 0 && !zero(zt)) break;
+    }
+  }
+  const size_t m = mnt753_domain_size(d0);
+  vector_Fr* vecs[3] = {ca, cb, cc};
+  const int dev[3] = {ca->device(), cb->device(), cc->device()};
+  if (dev[0] == dev[1] && dev[0] == dev[2]) {
+    DeviceScope on(dev[0]);
+    DeviceBuffer u(96 * m);
+    const uint64_t* p[3] = {ca->ptr(), cb->ptr(), cc->ptr()};
+    check(mnt753_domain_interp_at(domain_on<CURVE>(domain, dev[0]), st->t, p, 3, reinterpret_cast<uint64_t*>(u.ptr), st->abc, nullptr), "mnt753_domain_interp_at");
+  } else {
+    // sharded: every vector on the device and the domain object it lives on, before its chain of transforms
+    for (int k = 0; k < 3; ++k) {
+      DeviceScope on(dev[k]);
+      DeviceBuffer u(96 * m);
+      const uint64_t* p = vecs[k]->ptr();
+      check(mnt753_domain_interp_at(domain_on<CURVE>(domain, dev[k]), st->t, &p, 1, reinterpret_cast<uint64_t*>(u.ptr), st->abc + 12 * k, nullptr), "mnt753_domain_interp_at");
+    }
+  }
+  return st.release();
+}
+template <int CURVE> typename HIP_B::h_check_result HIP_B::h_check_finish(h_check_state* state, vector_Fr* h) {
+  std::unique_ptr<h_check_state> st(state);
+  mnt753_h_check_result res;
+  check(mnt753_h_check(domain_on<CURVE>(st->domain, h->device()), st->t, st->abc, h->ptr(), &res, nullptr), "mnt753_h_check");
+  h_check_result out;
+  out.ok = res.ok != 0;
+  memcpy(out.t, st->t, 96); memcpy(out.lhs, res.lhs, 96); memcpy(out.rhs, res.rhs, 96);
   return out;
 }
 template <int CURVE> double HIP_B::input_load_seconds(groth16_input* in) {

@@ -231,6 +231,31 @@ int mnt753_check_products(int curve, const uint64_t* a, const uint64_t* b, const
 int mnt753_domain_vanishing_at(mnt753_domain* d, const uint64_t* t, uint64_t* zt) { if (!d || !t || !zt) return fail(MNT753_EINVAL, "domain_vanishing_at: null argument"); memset(zt, 0, 96); return 0; }
 int mnt753_domain_lagrange_at(mnt753_domain* d, const uint64_t* t, uint64_t* u, void*) { if (!d || !t || !u) return fail(MNT753_EINVAL, "domain_lagrange_at: null argument"); memset(u, 0, 96 * d->m); return 0; }
 int mnt753_vec_powers(int curve, const uint64_t* t, uint64_t* out, size_t n, void*) { if (curve < 0 || curve > 1 || !t || (n && !out)) return fail(MNT753_EINVAL, "vec_powers: bad argument"); if (n) memset(out, 0, 96 * n); return 0; }
+int mnt753_vec_dot(int curve, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, void*) {
+  if (curve < 0 || curve > 1 || !out || (n && (!a || !b))) return fail(MNT753_EINVAL, "vec_dot: bad argument");
+  if (!g_ndev) return fail(MNT753_ENODEV, "no device");
+  touch_ro(a, 12 * n); touch_ro(b, 12 * n); memset(out, 0, 96); return 0;
+}
+int mnt753_poly_eval(int curve, const uint64_t* c, size_t n, const uint64_t* t, uint64_t* out, void*) {
+  if (curve < 0 || curve > 1 || !t || !out || (n && !c)) return fail(MNT753_EINVAL, "poly_eval: bad argument");
+  if (!g_ndev) return fail(MNT753_ENODEV, "no device");
+  touch_ro(c, 12 * n); memset(out, 0, 96); return 0;
+}
+int mnt753_domain_interp_at(mnt753_domain* d, const uint64_t* t, const uint64_t* const* vecs, int k, uint64_t* u, uint64_t* out, void*) {
+  if (!d || !t || !vecs || k < 1 || k > 3 || !u || !out) return fail(MNT753_EINVAL, "domain_interp_at: bad argument");
+  for (int j = 0; j < k; ++j) { if (!vecs[j]) return fail(MNT753_EINVAL, "domain_interp_at: null vector"); touch_ro(vecs[j], 12 * d->m); }
+  memset(u, 0, 96 * d->m); memset(out, 0, 96 * (size_t)k); return 0;
+}
+int mnt753_h_check(mnt753_domain* d, const uint64_t* t, const uint64_t* abc, const uint64_t* h, mnt753_h_check_result* out, void*) {
+  if (!d || !t || !abc || !h || !out) return fail(MNT753_EINVAL, "h_check: null argument");
+  touch_ro(h, 12 * (d->m + 1)); touch_ro(abc, 36); memset(out, 0, sizeof *out); out->ok = 1; return 0;
+}
+int mnt753_compute_h_checked(mnt753_domain* d, uint64_t* a, uint64_t* b, uint64_t* c, uint64_t* h, const uint64_t* t, mnt753_h_check_result* out, void* st) {
+  if (!d || !a || !b || !c || !h || !out) return fail(MNT753_EINVAL, "compute_h_checked: null argument");
+  if (t) touch_ro(t, 12);
+  if (int rc = mnt753_compute_h(d, a, b, c, h, st)) return rc;
+  memset(out, 0, sizeof *out); out->ok = 1; return 0;
+}
 int mnt753_r1cs_qap_plan(const mnt753_r1cs* r, mnt753_qap_plan* out) { if (!r || !out) return fail(MNT753_EINVAL, "r1cs_qap_plan: null argument"); memset(out, 0, sizeof *out); out->chunk_terms = 256; return 0; }
 int mnt753_r1cs_qap_at(mnt753_r1cs* r, mnt753_domain* d, const uint64_t* t, uint64_t* at, uint64_t* bt, uint64_t* ct, uint64_t* ht, uint64_t* zt, void*) {
   if (!r || !d || !t || !at || !bt || !ct || !ht || !zt) return fail(MNT753_EINVAL, "r1cs_qap_at: null argument");
