@@ -548,6 +548,31 @@ int mnt753_groth16_verify(const mnt753_vk* vk, const uint64_t* proofs, const uin
 #define MNT753_VERIFY_CHECK_SUBGROUP 1u
 int mnt753_groth16_verify_ex(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int on_device, unsigned flags, uint8_t* verdicts,
                              void* stream);
+/* Randomised batch verification: the n proofs folded into ONE final exponentiation.  An opt-in beside the
+ * exact calls above, with a different soundness statement.  proofs, inputs, on_device, stream and the chunking under
+ * mnt753_vk_set_workspace_cap as for mnt753_groth16_verify.  coefficients: n x 2 words in HOST memory, rho_i = word 0 + 2^64 word 1,
+ * 0 < rho_i < 2^128; they are an ARGUMENT, as the randomness of mnt753_groth16_generate is: the library draws nothing.  With
+ *     U_i = rho_i A_i,  T = sum rho_i C_i,  rho = sum rho_i,  c_j = sum_i rho_i x_ij mod r,  S = rho ABC[0] + sum_j c_j ABC[j + 1]
+ * the batch is accepted iff  FE( prod_i ML(U_i, B_i) ML(-S, G2::one()) ML(-T, delta_g2) ) == alpha_g1_beta_g2^rho:  per proof one
+ * stepped Miller loop with ONE line value per step and two 128-bit scalar multiplications in G1; the two stored pairs of the key, the
+ * final exponentiation and the power of alpha_g1_beta_g2 once per call.
+ * Soundness.  Let every A_i and C_i lie on its curve (G1 has cofactor 1), every B_i lie in G2, and beta_g2 and delta_g2 of the key lie
+ * in G2.  Then each proof's defect d_i = e(A_i, B_i) e(acc_i, G2::one())^-1 e(C_i, delta_g2)^-1 e(alpha_g1, beta_g2)^-1 lies in the
+ * order-r subgroup of GT and the check is prod d_i^rho_i == 1: if some d_i != 1 and the rho_i are drawn uniformly AFTER the proofs are
+ * fixed, it passes with probability at most 1 / (2^128 - 1).  Coefficients an adversary can predict prove nothing (two defects can
+ * cancel).  The curve checks of A, B, C and the subgroup test of every B_i (psi(B) == [t - 1] B on the running point of its Miller
+ * loop) are therefore part of THIS call, not a flag; beta_g2 and delta_g2 of the key remain the caller's duty (mnt753_check_subgroup),
+ * as for mnt753_groth16_verify_ex.
+ * status (host memory, n bytes, may be NULL): per proof 0, 1 (malformed, as for mnt753_groth16_verify) or 3 (B is not in the
+ * subgroup); there is no per-proof 2.  One difference from the per-proof verifier: acc_i is never formed, so "acc_i is the identity"
+ * is not reported as malformed (meeting that case needs a discrete-logarithm relation among the ABC points).
+ * *accepted = 1 iff every status byte is 0 and the folded equation holds; a rejected batch does not say WHICH proof is wrong: run
+ * mnt753_groth16_verify_ex with MNT753_VERIFY_CHECK_SUBGROUP to name it.  n = 0: *accepted = 1.  Returns 0, or a negative code:
+ * MNT753_EINVAL for a null pointer, a zero coefficient, n > 2^24 or memory on another device.  Workspace per proof of a chunk:
+ * 546 bytes, with public inputs 96 (num_inputs + 1) more, plus its staged copy if it arrives in host memory, and one GT element per
+ * 128 (MNT6753: 84) proofs.  Blocks until the verdict is there. */
+int mnt753_groth16_verify_folded(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int on_device,
+                                 const uint64_t* coefficients /* n x 2 words, host */, uint8_t* status /* n, host, may be NULL */, int* accepted, void* stream);
 
 /* ---- input validation (device) --------------------------------------------------------------------------
  * The reference prover trusts its files (unchecked fread, prover_reference_functions.cpp:48-116); what the reference HAS for the

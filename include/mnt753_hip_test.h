@@ -78,6 +78,16 @@ int mnt753_test_miller_loop(int curve, int split, const uint64_t* g1_affine, con
  * loop alone; the identity (the incomplete steps ended with Z = 0) as zero words. */
 int mnt753_test_g2_endomorphism(int curve, const uint64_t* g2_affine, size_t n, uint64_t* out_affine);
 int mnt753_test_g2_loop_multiple(int curve, const uint64_t* g2_affine, size_t n, uint64_t* out_affine);
+/* mnt753_groth16_verify_folded on host-memory proofs, inputs and coefficients with the parts of the fold handed out (host memory, any
+ * may be NULL): out_f the UNREDUCED product of the Miller values of the stepped pairs (rho_i A_i, B_i)
+ * (mnt753_gt_words words), out_s = rho ABC[0] + sum_j c_j ABC[j + 1] and out_t = sum rho_i C_i (affine wire form, 24 words each, the
+ * identity as zero words), out_rho = sum rho_i as an element of Fr (wire form, 12 words).  status and accepted as there.  The parts are
+ * filled whatever the verdict. */
+int mnt753_test_fold_parts(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, const uint64_t* coefficients, uint64_t* out_f,
+                           uint64_t* out_s, uint64_t* out_t, uint64_t* out_rho, uint8_t* status, int* accepted);
+/* milliseconds on the device (HIP events) of the stages of the calling thread's last mnt753_groth16_verify_folded / mnt753_test_fold_parts:
+ * [0] the scaling and the point sum, [1] the Miller loops and the products, [2] the tail (0 where it was skipped).  tools/bench_fold.py. */
+int mnt753_test_fold_last_timing(float out_ms[3]);
 
 /* mnt753_vec_dot (op 0: a = dev_a, b = dev_b) or mnt753_poly_eval (op 1: coefficients dev_a, t = host_t, dev_b unused) with at most
  * max_blocks blocks of 256 threads in the reducing launch (0: the device's own cap), so that a test reaches the second grid-stride trip

@@ -197,6 +197,15 @@ public:
   // elements are not tested by this call (check_subgroup above does that)
   static std::vector<uint8_t> verify(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *proofs, const uint64_t *inputs, size_t n,
                                      bool check_subgroup);
+  // the batch folded into ONE final exponentiation (mnt753_groth16_verify_folded): coefficients = n x 2 words,
+  // 0 < rho_i < 2^128, drawn by the caller AFTER the proofs are fixed; status per proof 0, 1 (malformed) or 3 (B not in the subgroup);
+  // accepted: every status is 0 and the folded equation holds.  A rejected batch does not name the wrong proof: verify(.., true) does.
+  struct folded_verdict {
+    bool accepted;
+    std::vector<uint8_t> status;
+  };
+  static folded_verdict verify_folded(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *proofs, const uint64_t *inputs, size_t n,
+                                      const uint64_t *coefficients);
   // raw access for tests / tools
   static const uint64_t *G1_words(const G1 *a);
   static const uint64_t *G2_words(const G2 *a);

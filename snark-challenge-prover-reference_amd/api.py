@@ -63,6 +63,11 @@ class HCheckResult(C.Structure):
     _fields_ = [("ok", C.c_int32), ("reserved", C.c_int32), ("lhs", C.c_uint64 * 12), ("rhs", C.c_uint64 * 12)]
 
 
+# Names an OLDER build of the library may lack: empty in the product.  An A/B tool that times a build from before a call existed
+# (tools/bench_fold.py with MNT753_LIB) adds the name here before the first lib(); every other name must resolve.
+OPTIONAL_SYMBOLS = set()
+
+
 def lib_path():
     """The product library next to this file; MNT753_LIB names another build of it (development A/B runs: an experimental
     variant is loaded from where it was built instead of being copied over the product file)."""
@@ -188,8 +193,11 @@ def lib():
         "mnt753_vk_accumulate": (i, [vp, u64p, sz, u64p]),
         "mnt753_groth16_verify": (i, [vp, vp, vp, sz, i, vp, vp]),
         "mnt753_groth16_verify_ex": (i, [vp, vp, vp, sz, i, C.c_uint, vp, vp]),
+        "mnt753_groth16_verify_folded": (i, [vp, vp, vp, sz, i, u64p, vp, C.POINTER(C.c_int), vp]),
     }
     for name, (res, args) in sig.items():
+        if name in OPTIONAL_SYMBOLS and not hasattr(L, name):
+            continue
         fn = getattr(L, name)   # AttributeError here = the library does not export what the header declares
         fn.restype, fn.argtypes = res, args
     _LIB = L
@@ -229,6 +237,8 @@ def test_lib():
         "mnt753_test_g2_endomorphism": (i, [i, u64p, sz, u64p]),
         "mnt753_test_g2_loop_multiple": (i, [i, u64p, sz, u64p]),
         "mnt753_test_reduce_capped": (i, [i, i, C.c_void_p, C.c_void_p, sz, u64p, C.c_uint, u64p]),
+        "mnt753_test_fold_parts": (i, [C.c_void_p, u64p, u64p, sz, u64p, u64p, u64p, u64p, u64p, C.c_void_p, C.POINTER(C.c_int)]),
+        "mnt753_test_fold_last_timing": (i, [C.POINTER(C.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1154,10 +1164,17 @@ class VerificationKey:
         constructor (mnt753_vk_create) does not test membership itself."""
         return check_subgroup(self.curve, G2, self._g2)
 
-    def verify(self, proofs, inputs, on_device=False, n=None, stream=None, check_subgroup=False):
+    def verify(self, proofs, inputs, on_device=False, n=None, stream=None, check_subgroup=False, fold=False):
         """proofs: n x (A | B | C) affine wire words, inputs: n x num_inputs Fr (numpy arrays, or device addresses with on_device and n)
         -> numpy uint8 verdicts [n]: 0 accepted, 1 malformed, 2 the pairing check failed; with check_subgroup also 3: B is not in the
-        order-r subgroup of the twist (mnt753_groth16_verify_ex with MNT753_VERIFY_CHECK_SUBGROUP)"""
+        order-r subgroup of the twist (mnt753_groth16_verify_ex with MNT753_VERIFY_CHECK_SUBGROUP).
+        fold: verify_folded() with fresh coefficients first -- an accepted batch is all zeros after one final exponentiation -- and, if
+        the fold rejects, the per-proof pass with check_subgroup, which names the proofs."""
+        if fold:
+            accepted, status = self.verify_folded(proofs, inputs, on_device=on_device, n=n, stream=stream)
+            if accepted:
+                return status
+            return self.verify(proofs, inputs, on_device=on_device, n=n, stream=stream, check_subgroup=True)
         pw = 48 + affine_words(self.curve, G2)
         pp, cnt, keep1 = _input_ptr(proofs, on_device, pw, n)
         if self.num_inputs:
@@ -1176,6 +1193,52 @@ class VerificationKey:
             _check(rc, "mnt753_groth16_verify")
         return verdicts
 
+    def _fold_args(self, proofs, inputs, coefficients, on_device, n):
+        pw = 48 + affine_words(self.curve, G2)
+        pp, cnt, keep1 = _input_ptr(proofs, on_device, pw, n)
+        if self.num_inputs:
+            pi, cnt2, keep2 = _input_ptr(inputs, on_device, 12 * self.num_inputs, n)
+            if cnt2 != cnt:
+                raise Mnt753Error("verify_folded: one row of inputs per proof")
+        else:
+            pi, keep2 = C.c_void_p(), None
+        if coefficients is None:
+            import secrets
+            coefficients = [secrets.randbelow(2 ** 128 - 1) + 1 for _ in range(cnt)]
+        if isinstance(coefficients, np.ndarray) and coefficients.dtype == np.uint64:
+            co = np.ascontiguousarray(coefficients).reshape(-1)
+        else:
+            co = np.array([(int(v) >> (64 * k)) & (2 ** 64 - 1) for v in coefficients for k in range(2)], dtype=np.uint64)
+        if co.size != 2 * cnt:
+            raise Mnt753Error("verify_folded: one 128-bit coefficient per proof")
+        return pp, pi, cnt, co, (keep1, keep2)
+
+    def verify_folded(self, proofs, inputs, coefficients=None, on_device=False, n=None, stream=None):
+        """mnt753_groth16_verify_folded: the batch under ONE final exponentiation -> (accepted, status [n]:
+        0, 1 malformed, 3 B not in the subgroup).  coefficients: n integers 0 < rho_i < 2^128 (or [n, 2] uint64 words); None draws them
+        from `secrets` -- they must not be predictable by whoever made the proofs.  A rejected batch does not name the wrong proof:
+        verify(.., fold=True) falls back to the per-proof pass."""
+        pp, pi, cnt, co, keep = self._fold_args(proofs, inputs, coefficients, on_device, n)
+        status = np.zeros(cnt, dtype=np.uint8)
+        accepted = C.c_int(0)
+        st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+        _check(lib().mnt753_groth16_verify_folded(self._h, pp, pi, cnt, 1 if on_device else 0, co.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                  C.c_void_p(status.ctypes.data), C.byref(accepted), st), "mnt753_groth16_verify_folded")
+        return bool(accepted.value), status
+
+    def test_fold_parts(self, proofs, inputs, coefficients):
+        """mnt753_test_fold_parts (test library) on host arrays -> dict: f (the unreduced product), s, t (affine wire form), rho (Fr
+        wire form), status, accepted"""
+        pp, pi, cnt, co, keep = self._fold_args(proofs, inputs, coefficients, False, None)
+        u64p = C.POINTER(C.c_uint64)
+        f, s, t, rho = (np.zeros(k, dtype=np.uint64) for k in (gt_words(self.curve), 24, 24, 12))
+        status = np.zeros(cnt, dtype=np.uint8)
+        accepted = C.c_int(0)
+        _check(test_lib().mnt753_test_fold_parts(self._h, C.cast(pp, u64p), C.cast(pi, u64p), cnt, co.ctypes.data_as(u64p), f.ctypes.data_as(u64p),
+                                                 s.ctypes.data_as(u64p), t.ctypes.data_as(u64p), rho.ctypes.data_as(u64p),
+                                                 C.c_void_p(status.ctypes.data), C.byref(accepted)), "mnt753_test_fold_parts")
+        return {"f": f, "s": s, "t": t, "rho": rho, "status": status, "accepted": bool(accepted.value)}
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib().mnt753_vk_destroy(self._h)
@@ -1186,6 +1249,13 @@ class VerificationKey:
             self.close()
         except Exception:
             pass
+
+
+def test_fold_last_timing():
+    """mnt753_test_fold_last_timing (test library): milliseconds of the scale, Miller-and-fold and tail stages of the last folded call"""
+    out = (C.c_float * 3)()
+    _check(test_lib().mnt753_test_fold_last_timing(out), "mnt753_test_fold_last_timing")
+    return [float(v) for v in out]
 
 
 def test_tower_op(curve, split, op, a, b=None):

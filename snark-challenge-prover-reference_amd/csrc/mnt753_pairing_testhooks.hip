@@ -2,10 +2,12 @@
 // The tower of tower753.hip.h and the two halves of the pairing (pairing_kernels.hip.h) exposed element-wise, in the one-lane and in
 // the lane-split form, so that tests/test_pairing_gpu.py can pin them against the Python-integer model (tests/pairing_ref.py): an
 // error in the Miller loop that the final exponentiation happens to map to the right GT element still shows in the unreduced value.
+// mnt753_test_fold_parts hands out the parts of the folded verification (csrc/mnt753_fold.hip) the same way.
 #include <hip/hip_runtime.h>
 
 #include "common_host.hpp"
 #include "../../include/mnt753_hip_test.h"
+#include "fold_api.hpp"
 #include "pairing_kernels.hip.h"
 
 using namespace mnt753;
@@ -118,4 +120,16 @@ extern "C" int mnt753_test_miller_loop(int curve, int split, const uint64_t* g1_
   if (n == 0) return 0;
   if (curve == MNT753_CURVE_MNT4753) return split ? run_miller<Mnt4G2S>(g1_affine, g2_affine, n, out) : run_miller<Mnt4G2>(g1_affine, g2_affine, n, out);
   return split ? run_miller<Mnt6G2S>(g1_affine, g2_affine, n, out) : run_miller<Mnt6G2>(g1_affine, g2_affine, n, out);
+}
+
+extern "C" int mnt753_test_fold_parts(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, const uint64_t* coefficients, uint64_t* out_f,
+                                      uint64_t* out_s, uint64_t* out_t, uint64_t* out_rho, uint8_t* status, int* accepted) {
+  FoldParts parts;
+  parts.f = out_f; parts.s = out_s; parts.t = out_t; parts.rho = out_rho;
+  return groth16_verify_folded_parts(vk, proofs, inputs, n, 0, coefficients, status, accepted, nullptr, &parts);
+}
+extern "C" int mnt753_test_fold_last_timing(float out_ms[3]) {
+  if (!out_ms) return set_error(MNT753_EINVAL, "test_fold_last_timing: bad argument");
+  groth16_fold_last_timing(out_ms);
+  return 0;
 }

@@ -758,7 +758,7 @@ __global__ void __launch_bounds__(256, 1) k_groth16_verify(const uint32_t* __res
 struct SubgroupReport {
   unsigned long long n_bad, key;
 };
-__global__ void k_subgroup_report_init(SubgroupReport* rec) {
+static __global__ void k_subgroup_report_init(SubgroupReport* rec) {   // (static: the header serves more than one unit of the library)
   rec->n_bad = 0;
   rec->key = ~0ull;
 }

@@ -638,13 +638,31 @@ static bool read_all_words(const char* path, std::vector<uint64_t>& out) {
   fclose(f);
   return true;
 }
-static int vk_command(int curve, bool verify, const std::vector<const char*>& pos, bool check_subgroup = false) {
+// --fold: the batch through B::verify_folded first (one final exponentiation); its coefficients come from
+// --fold-coefficients <file> (n x 16 bytes, none zero) or from getrandom.  Accepted: one line "VERIFIED <n> proofs (folded)", exit 0.
+// Rejected: the per-proof pass of --check-subgroup names the proofs, exit 3.  The key's beta_g2 and delta_g2 are tested first, as
+// with --check-subgroup: the fold is sound only with both in G2.
+static bool fold_coefficients(const char* path, size_t n, std::vector<uint64_t>& out) {
+  out.assign(2 * n, 0);
+  if (path) {
+    std::vector<uint64_t> w;
+    if (!read_all_words(path, w)) return false;
+    if (w.size() != 2 * n) { fprintf(stderr, "main_hip: %s does not hold one 128-bit coefficient per proof\n", path); return false; }
+    out = w;
+    return true;
+  }
+  for (size_t k = 0; k < n; ++k)
+    while (!(out[2 * k] | out[2 * k + 1]))
+      if (getrandom(&out[2 * k], 16, 0) != 16) { fprintf(stderr, "main_hip: getrandom failed\n"); return false; }
+  return true;
+}
+static int vk_command(int curve, bool verify, const std::vector<const char*>& pos, bool check_subgroup = false, bool fold = false, const char* fold_file = nullptr) {
   const size_t w2 = mnt753_affine_words(curve, MNT753_G2);
   std::vector<uint64_t> el;
   if (!read_all_words(pos[0], el)) return 1;
   if (el.size() < 48 + 2 * w2 || (el.size() - 24 - 2 * w2) % 24) { fprintf(stderr, "main_hip: %s does not hold alpha_g1 | beta_g2 | delta_g2 | ABC_g1\n", pos[0]); return 3; }
   const size_t num_inputs = (el.size() - 24 - 2 * w2) / 24 - 1;
-  std::vector<uint64_t> inputs, proofs;
+  std::vector<uint64_t> inputs, proofs, coef;
   if (verify) {
     FILE* f = fopen(pos[1], "rb");
     inputs.resize(12 * (num_inputs + 1));
@@ -659,6 +677,7 @@ static int vk_command(int curve, bool verify, const std::vector<const char*>& po
       if (one.size() != 48 + w2) { fprintf(stderr, "main_hip: %s is not a proof A | B | C\n", pos[k]); return 3; }
       proofs.insert(proofs.end(), one.begin(), one.end());
     }
+    if (fold && !fold_coefficients(fold_file, pos.size() - 2, coef)) return 1;
   }
   if (mnt753_init(0) != 0) { fprintf(stderr, "main_hip: %s\n", mnt753_last_error()); return 1; }
   if (verify) {
@@ -677,6 +696,11 @@ static int vk_command(int curve, bool verify, const std::vector<const char*>& po
         if (n_bad) {
           fprintf(stderr, "main_hip: %s of the key: %s\n", first_bad == 0 ? "beta_g2" : "delta_g2", mnt4753_hip::check_reason_text(reason));
           return 3;
+        }
+        if (fold) {
+          const bool accepted = curve == 0 ? mnt4753_hip::verify_folded(el.data(), num_inputs, proofs.data(), per_proof.data(), n, coef.data()).accepted
+                                           : mnt6753_hip::verify_folded(el.data(), num_inputs, proofs.data(), per_proof.data(), n, coef.data()).accepted;
+          if (accepted) { printf("VERIFIED %zu proofs (folded)\n", n); return 0; }
         }
         verdicts = curve == 0 ? mnt4753_hip::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n, true)
                               : mnt6753_hip::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n, true);
@@ -716,21 +740,26 @@ int main(int argc, char** argv) {
     const int curve = !strcmp(argv[1], "MNT4753") ? 0 : (!strcmp(argv[1], "MNT6753") ? 1 : -1);
     if (curve < 0) { fprintf(stderr, "unknown curve %s\n", argv[1]); return 2; }
     std::vector<const char*> pos;
-    bool check_subgroup = false;
+    bool check_subgroup = false, fold = false;
+    const char* fold_file = nullptr;
     for (int i = 3; i < argc; ++i) {
       if (verify && !strcmp(argv[i], "--check-subgroup")) { check_subgroup = true; continue; }
+      if (verify && !strcmp(argv[i], "--fold")) { fold = check_subgroup = true; continue; }
+      if (verify && !strcmp(argv[i], "--fold-coefficients") && i + 1 < argc) { fold_file = argv[++i]; continue; }
       if (argv[i][0] == '-') { fprintf(stderr, "main_hip: unknown option %s\n", argv[i]); return 2; }
       pos.push_back(argv[i]);
     }
     if (verify ? pos.size() < 3 : pos.size() != 2) {
-      fprintf(stderr, "usage: %s MNT4753|MNT6753 vk <vk_elements.bin> <out>\n       %s MNT4753|MNT6753 verify <vk_elements.bin> <input_or_witness> <proof> [<proof> ...] [--check-subgroup]\n"
+      fprintf(stderr, "usage: %s MNT4753|MNT6753 vk <vk_elements.bin> <out>\n       %s MNT4753|MNT6753 verify <vk_elements.bin> <input_or_witness> <proof> [<proof> ...] [--check-subgroup] [--fold [--fold-coefficients <file>]]\n"
                       "  vk: writes the complete verification key (with the GT element e(alpha_g1, beta_g2)) in the reference's vk.txt format.\n"
                       "  verify: prints VERIFIED or REJECTED per proof; exit code 0 if every proof is accepted, 3 otherwise.\n"
                       "  --check-subgroup: beta_g2 and delta_g2 of the key and B of every proof must lie in G2, the order-r subgroup of the twist;\n"
-                      "    a key that fails is named and nothing is verified (exit 3), such a proof prints REJECTED (B not in the subgroup).\n", argv[0], argv[0]);
+                      "    a key that fails is named and nothing is verified (exit 3), such a proof prints REJECTED (B not in the subgroup).\n"
+                      "  --fold: the batch under one final exponentiation first (random coefficients, or n x 16 bytes from --fold-coefficients);\n"
+                      "    accepted: one line naming the count, exit 0; rejected: the per-proof lines of --check-subgroup, exit 3.\n", argv[0], argv[0]);
       return 2;
     }
-    return vk_command(curve, verify, pos, check_subgroup);
+    return vk_command(curve, verify, pos, check_subgroup, fold, fold_file);
   }
   if (argc >= 3 && !strcmp(argv[2], "generate")) {
     const int curve = !strcmp(argv[1], "MNT4753") ? 0 : (!strcmp(argv[1], "MNT6753") ? 1 : -1);

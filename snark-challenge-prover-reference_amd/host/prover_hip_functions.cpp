@@ -1488,6 +1488,19 @@ template <int CURVE> std::vector<uint8_t> HIP_B::verify(const uint64_t* vk_eleme
   if (rc < 0) check(rc, "mnt753_groth16_verify");
   return verdicts;
 }
+template <int CURVE> typename HIP_B::folded_verdict HIP_B::verify_folded(const uint64_t* vk_elements, size_t num_inputs, const uint64_t* proofs, const uint64_t* inputs,
+                                                                        size_t n, const uint64_t* coefficients) {
+  const size_t w2 = mnt753_affine_words(CURVE, MNT753_G2);
+  mnt753_vk* vk = nullptr;
+  check(mnt753_vk_create(CURVE, vk_elements, vk_elements + 24, vk_elements + 24 + w2, vk_elements + 24 + 2 * w2, num_inputs, &vk), "mnt753_vk_create");
+  folded_verdict out{false, std::vector<uint8_t>(n)};
+  int accepted = 0;
+  const int rc = mnt753_groth16_verify_folded(vk, proofs, inputs, n, 0, coefficients, out.status.data(), &accepted, nullptr);
+  mnt753_vk_destroy(vk);
+  check(rc, "mnt753_groth16_verify_folded");
+  out.accepted = accepted != 0;
+  return out;
+}
 
 template class mnt753_hip_impl<0>;
 template class mnt753_hip_impl<1>;

@@ -324,6 +324,17 @@ int mnt753_groth16_verify_ex(const mnt753_vk* vk, const uint64_t* proofs, const 
 int mnt753_groth16_verify(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int od, uint8_t* verdicts, void* st) {
   return mnt753_groth16_verify_ex(vk, proofs, inputs, n, od, 0u, verdicts, st);
 }
+// MNT753_STUB_REJECT rejects the fold as it rejects every proof
+int mnt753_groth16_verify_folded(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int, const uint64_t* coefficients, uint8_t* status,
+                                 int* accepted, void*) {
+  if (!vk || !accepted || (n && (!proofs || !coefficients))) return fail(MNT753_EINVAL, "groth16_verify_folded: bad argument");
+  touch_ro(proofs, n * (48 + mnt753_affine_words(vk->curve, MNT753_G2))); touch_ro(inputs, 12 * vk->num_inputs * n); touch_ro(coefficients, 2 * n);
+  for (size_t i = 0; i < n; ++i)
+    if (!(coefficients[2 * i] | coefficients[2 * i + 1])) return fail(MNT753_EINVAL, "groth16_verify_folded: a coefficient is zero");
+  for (size_t i = 0; status && i < n; ++i) status[i] = 0;
+  *accepted = getenv("MNT753_STUB_REJECT") == nullptr;
+  return 0;
+}
 int mnt753_group_generator(int curve, int group, uint64_t* out) {
   if (curve < 0 || curve > 1 || (group != MNT753_G1 && group != MNT753_G2) || !out) return fail(MNT753_EINVAL, "group_generator: bad argument");
   for (size_t i = 0; i < mnt753_affine_words(curve, group); ++i) out[i] = 1 + i;
