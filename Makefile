@@ -37,7 +37,7 @@ $(PAIRING_TEST): tools/host_tests/pairing_wrapper_test.cpp $(HOST)/prover_hip_fu
 $(HCHECK_TEST): tools/host_tests/h_check_wrapper_test.cpp $(HOST)/prover_hip_functions.cpp include/prover_hip_functions.hpp include/mnt753_hip.h $(LIB)
 	g++ -O2 -std=c++17 -pthread -o $@ tools/host_tests/h_check_wrapper_test.cpp $(HOST)/prover_hip_functions.cpp -L$(PKG) -lmnt753_hip -Wl,-rpath,'$$ORIGIN'
 
-$(MAIN): $(HOST)/main.cpp $(HOST)/prover_hip_functions.cpp include/prover_hip_functions.hpp include/mnt753_hip.h $(LIB)
+$(MAIN): $(HOST)/main.cpp $(HOST)/main_io.hpp $(HOST)/prover_hip_functions.cpp include/prover_hip_functions.hpp include/mnt753_hip.h $(LIB)
 	g++ -O2 -std=c++17 -pthread -o $@ $(HOST)/main.cpp $(HOST)/prover_hip_functions.cpp -L$(PKG) -lmnt753_hip -Wl,-rpath,'$$ORIGIN'
 
 # per-object dependency files (-MMD): a change to one header rebuilds the translation units that include it, not all of them
@@ -65,14 +65,14 @@ oracle:
 SAN_SRCS := $(HOST)/main.cpp $(HOST)/prover_hip_functions.cpp tools/stub_abi/stub_mnt753.cpp
 asan: $(BUILD)/san/main_hip_asan $(BUILD)/san/host_pairing_check_asan
 tsan: $(BUILD)/san/main_hip_tsan
-$(BUILD)/san/main_hip_asan: $(SAN_SRCS) include/prover_hip_functions.hpp include/mnt753_hip.h
+$(BUILD)/san/main_hip_asan: $(SAN_SRCS) $(HOST)/main_io.hpp include/prover_hip_functions.hpp include/mnt753_hip.h
 	@mkdir -p $(BUILD)/san
 	g++ -O1 -g -std=c++17 -pthread -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ $(SAN_SRCS)
 # the tower and the pairing through the one-lane fields on the host (tools/host_pairing_check.cpp), a stand-alone program: run it directly
 $(BUILD)/san/host_pairing_check_asan: tools/host_pairing_check.cpp $(HDRS)
 	@mkdir -p $(BUILD)/san
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ tools/host_pairing_check.cpp
-$(BUILD)/san/main_hip_tsan: $(SAN_SRCS) include/prover_hip_functions.hpp include/mnt753_hip.h
+$(BUILD)/san/main_hip_tsan: $(SAN_SRCS) $(HOST)/main_io.hpp include/prover_hip_functions.hpp include/mnt753_hip.h
 	@mkdir -p $(BUILD)/san
 	g++ -O1 -g -std=c++17 -pthread -fsanitize=thread -o $@ $(SAN_SRCS)
 

@@ -600,7 +600,7 @@ template <int CURVE, int GROUP, class P> static void resolve_t(P* p) {
     for (size_t k = 0; k < parts.size(); ++k) in[(size_t)p->pending->devs[k]] = parts[k].data();
     std::vector<uint64_t> out((size_t)n_dev * pw);
     const int rc = mnt753_exchange_points(in.data(), pw, out.data());
-    const bool trace = getenv("MNT753_TRACE") && atoi(getenv("MNT753_TRACE"));
+    const bool trace = trace_on();
     if (rc == 0) {
       if (trace) fprintf(stderr, "mnt753: partial points over RCCL: all-gather of %zu u64 x %d devices in %.1f us\n", pw, n_dev, mnt753_exchange_last_us());
       parts.clear();
@@ -637,8 +637,7 @@ template <int CURVE> void HIP_B::init_public_params() {
     // every ordered pair the sharded prover copies between: cb / cc 1 -> 0 and 2 -> 0, slices of coefficients_for_H 0 -> g, operands
     // of the B:: vector calls between any two (operand_on).  The destination's copy engine reads the source's memory; without peer
     // access the copy stages through the host.  One line per pair under MNT753_TRACE=1.
-    const char* e = getenv("MNT753_TRACE");
-    const bool trace = e && atoi(e);
+    const bool trace = trace_on();
     static const char* const names[] = {"same GPU (logical devices share it)", "direct (peer access enabled)", "staged through host memory (no peer access)"};
     for (int a = 0; a < g_n_devices; ++a)
       for (int b = 0; b < g_n_devices; ++b) {
@@ -927,7 +926,7 @@ template <int CURVE>
 static std::shared_ptr<PendingMsm> start_fused_c(typename HIP_B::groth16_params* p, const ScalarSource& h, const ScalarSource& w_L, const ScalarSource& w, const uint64_t* r) {
   const size_t d = p->d, m = p->m, n = d + 2 * m;
   ShardedBases& sb = *p->HLB;
-  if (const char* e = getenv("MNT753_TRACE")) { if (atoi(e)) fprintf(stderr, "mnt753: C = Ht + Lt + r Bt1 as one MSM over H | L | B1 (%zu points, %zu device%s)\n", n, sb.parts.size(), sb.parts.size() > 1 ? "s" : ""); }
+  if (trace_on()) fprintf(stderr, "mnt753: C = Ht + Lt + r Bt1 as one MSM over H | L | B1 (%zu points, %zu device%s)\n", n, sb.parts.size(), sb.parts.size() > 1 ? "s" : "");
   if (!sb.interleaved) {
     auto sc = std::make_shared<DeviceBuffer>(96 * n);
     uint64_t* s = reinterpret_cast<uint64_t*>(sc->ptr);
@@ -1246,7 +1245,7 @@ template <int CURVE> typename HIP_B::vector_Fr* HIP_B::compute_H_fused(evaluatio
     const uint64_t* cp = operand_on(cc, da, m, keep);
     check(mnt753_compute_h_finish(domain_on<CURVE>(domain, da), ca->ptr(), bp, cp, reinterpret_cast<uint64_t*>(h->ptr), nullptr), "mnt753_compute_h_finish");
     keep_alive(out->keep, keep);
-    if (const char* e = getenv("MNT753_TRACE")) { if (atoi(e)) fprintf(stderr, "mnt753: compute_H over devices %d / %d / %d (chains where ca / cb / cc live, finish on %d)\n", da, db, dc, da); }
+    if (trace_on()) fprintf(stderr, "mnt753: compute_H over devices %d / %d / %d (chains where ca / cb / cc live, finish on %d)\n", da, db, dc, da);
     verdict();
   } catch (...) { delete checking; delete out; throw; }
   return out;
