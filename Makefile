@@ -10,9 +10,9 @@ LIB   := $(PKG)/libmnt753_hip.so
 # known-answer hooks.  Links against the product library; nothing of the product links against it.
 TESTLIB := $(PKG)/libmnt753_hip_test.so
 
-HIP_SRCS := mnt753_core.hip mnt753_msm.hip msm_sort.hip msm_inst_mnt4g1.hip msm_inst_mnt4g2.hip msm_inst_mnt6g1.hip msm_inst_mnt6g2.hip mnt753_fft.hip mnt753_synth.hip mnt753_r1cs.hip mnt753_exchange.hip mnt753_selftest.hip mnt753_validate.hip mnt753_batch_exp.hip batch_exp_inst_mnt4g1.hip batch_exp_inst_mnt4g2.hip batch_exp_inst_mnt6g1.hip batch_exp_inst_mnt6g2.hip mnt753_keygen.hip mnt753_pairing.hip mnt753_fold.hip
+HIP_SRCS := mnt753_core.hip mnt753_msm.hip msm_sort.hip msm_inst_mnt4g1.hip msm_inst_mnt4g2.hip msm_inst_mnt6g1.hip msm_inst_mnt6g2.hip mnt753_fft.hip mnt753_synth.hip mnt753_r1cs.hip mnt753_exchange.hip mnt753_selftest.hip mnt753_validate.hip mnt753_batch_exp.hip batch_exp_inst_mnt4g1.hip batch_exp_inst_mnt4g2.hip batch_exp_inst_mnt6g1.hip batch_exp_inst_mnt6g2.hip mnt753_keygen.hip mnt753_pairing.hip mnt753_fold.hip mnt753_compress.hip
 HIP_OBJS := $(addprefix $(BUILD)/,$(HIP_SRCS:.hip=.o))
-TEST_SRCS := mnt753_testhooks.hip mnt753_synth_points.hip mnt753_pairing_testhooks.hip
+TEST_SRCS := mnt753_testhooks.hip mnt753_synth_points.hip mnt753_pairing_testhooks.hip mnt753_compress_testhooks.hip
 TEST_OBJS := $(addprefix $(BUILD)/,$(TEST_SRCS:.hip=.o))
 HDRS := $(wildcard $(CSRC)/*.hpp $(CSRC)/*.hip.h $(CSRC)/*.h include/*.h)
 
@@ -63,7 +63,7 @@ oracle:
 # Host-only sanitizer builds (no GPU needed, GPU sanitizers do not exist on the pool): main.cpp + the wrapper over a TEST STUB of the
 # C ABI (tools/stub_abi: host memory, no arithmetic) under ASan + UBSan and under TSan.  tests/test_sanitizers_cpu.py runs them.
 SAN_SRCS := $(HOST)/main.cpp $(HOST)/prover_hip_functions.cpp tools/stub_abi/stub_mnt753.cpp
-asan: $(BUILD)/san/main_hip_asan $(BUILD)/san/host_pairing_check_asan
+asan: $(BUILD)/san/main_hip_asan $(BUILD)/san/host_pairing_check_asan $(BUILD)/san/host_sqrt_check_asan
 tsan: $(BUILD)/san/main_hip_tsan
 $(BUILD)/san/main_hip_asan: $(SAN_SRCS) $(HOST)/main_io.hpp include/prover_hip_functions.hpp include/mnt753_hip.h
 	@mkdir -p $(BUILD)/san
@@ -72,6 +72,11 @@ $(BUILD)/san/main_hip_asan: $(SAN_SRCS) $(HOST)/main_io.hpp include/prover_hip_f
 $(BUILD)/san/host_pairing_check_asan: tools/host_pairing_check.cpp $(HDRS)
 	@mkdir -p $(BUILD)/san
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ tools/host_pairing_check.cpp
+# the square root of fp_sqrt.hip.h through the base fields and the one-lane extension fields on the host (tools/host_sqrt_check.cpp),
+# a stand-alone program: run it directly
+$(BUILD)/san/host_sqrt_check_asan: tools/host_sqrt_check.cpp $(HDRS)
+	@mkdir -p $(BUILD)/san
+	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ tools/host_sqrt_check.cpp
 $(BUILD)/san/main_hip_tsan: $(SAN_SRCS) $(HOST)/main_io.hpp include/prover_hip_functions.hpp include/mnt753_hip.h
 	@mkdir -p $(BUILD)/san
 	g++ -O1 -g -std=c++17 -pthread -fsanitize=thread -o $@ $(SAN_SRCS)

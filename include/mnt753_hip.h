@@ -612,6 +612,52 @@ int mnt753_check_products(int curve, const uint64_t* dev_a, const uint64_t* dev_
  * mnt753_r1cs_evaluate into scratch vectors, then mnt753_check_products; first_bad = the lowest unsatisfied constraint row. */
 int mnt753_r1cs_check(mnt753_r1cs* r, const uint64_t* dev_w, mnt753_check_report* out, void* stream);
 
+/* ---- compressed points (device; the stream records on the host) ------------------------------------------
+ * libff's default point format (USE_PT_COMPRESSION; the challenge reference builds with NO_PT_COMPRESSION): x and one bit of y,
+ * operator<< / operator>> of depends/libff/libff/algebra/curves/mnt753/mnt4753/mnt4753_g1.cpp:389-450, mnt4753_g2.cpp:419-460 and the
+ * two mnt6753 files.  The PACKED compressed form of n points of (curve, group):
+ *   x:     n x mnt753_compressed_words words, the x coordinate exactly as in the affine wire form (Montgomery words, c0 | c1 | c2);
+ *   flags: n bytes; bit 0 = the parity of y as an INTEGER in [0, q), out of Montgomery form (G2: of y.c0) -- libff's
+ *          Y.as_bigint().data[0] & 1; bit 1 = the identity; bits 2-7 zero.
+ * mnt753_compress_points: affine wire points -> (x, flags); the identity (all words of y zero) gives x all zero and flag 2.  It
+ * VALIDATES NOTHING, like libff's operator<<: a point off its curve is compressed as it stands.
+ * mnt753_decompress_points: (x, flags) -> affine wire points and a report as mnt753_check_points fills it.  Per point, the first
+ * rule that applies: a flag bit 2-7 set or a component of x >= q -> MNT753_BAD_NONCANONICAL; the identity flag -> zero words, good,
+ * whatever x holds; x^3 + a x + b (G2: the twist's a', b') not a square, or zero -> MNT753_BAD_OFF_CURVE (for zero the only point has
+ * y = 0, which the wire form reads as the identity and which lies in neither group); otherwise y is the root whose parity is bit 0.
+ * A bad point's output is all-zero words, its neighbours are not disturbed.  The output goes straight into mnt753_bases_create.
+ * One lane per G1 point, one lane group (2 / 3 lanes) per G2 point; the square root (csrc/fp_sqrt.hip.h) has
+ * no data-dependent control flow.  A DEPARTURE from libff, in a case its format leaves open: for a G2 point with y.c0 = 0, y != 0 both
+ * roots carry flag 0 and libff returns whichever its loop lands on; here it is the root whose first non-zero higher component is even,
+ * whatever bit 0 says.
+ * Conventions of the validation calls above: n = 0 gives an all-zero report, null pointers and bad ids are MNT753_EINVAL, no device
+ * is MNT753_ENODEV, a malformed input is a result and not a failed call, on_device != 0: every pointer but the report is a device
+ * pointer on the current device (16-byte aligned, as every wire array). */
+size_t mnt753_compressed_words(int curve, int group);            /* 12, 24 (MNT4753 G2) or 36 (MNT6753 G2); 0 for bad ids */
+int mnt753_compress_points(int curve, int group, const uint64_t* affine, int on_device, size_t n, uint64_t* x_out, uint8_t* flags_out, void* stream);
+int mnt753_decompress_points(int curve, int group, const uint64_t* x, const uint8_t* flags, int on_device, size_t n, uint64_t* affine_out,
+                             mnt753_check_report* out, void* stream);
+/* mnt753_groth16_verify_ex on compressed proofs.  x: n x (x_A | x_B | x_C), 24 + mnt753_compressed_words(curve, MNT753_G2) words per
+ * proof; flags: n x 3 bytes (A, B, C); inputs, on_device, verify_flags, verdicts, stream and the return value as there.  A chunk is
+ * decompressed on the device into the affine staging buffer of the per-proof verifier, then the same kernels run: the verdicts are
+ * those of mnt753_decompress_points followed by mnt753_groth16_verify_ex, where verdict 1 (malformed) also covers every decompression
+ * failure and an identity flag on A, B or C.  Chunks stay under mnt753_vk_set_workspace_cap; per proof of a chunk, on top of the
+ * 194 + 96 num_inputs bytes of mnt753_groth16_verify: 8 (48 + mnt753_affine_words(curve, MNT753_G2)) bytes for the decompressed proof
+ * (768 / 960), and for a batch in host memory 8 (24 + compressed words of G2) + 3 (387 / 483) instead of the staged affine copy.
+ * The folded verifier takes no compressed proofs. */
+int mnt753_groth16_verify_compressed(const mnt753_vk* vk, const uint64_t* x /* n x (x_A|x_B|x_C) */, const uint8_t* flags /* n x 3 */,
+                                     const uint64_t* inputs, size_t n, int on_device, unsigned verify_flags, uint8_t* verdicts, void* stream);
+/* libff's stream records of the packed form, host only (no device needed): under BINARY_OUTPUT + MONTGOMERY_OUTPUT, where
+ * OUTPUT_SEPARATOR is empty (serialization.hpp:63-66), one point is the byte '0' or '1' (is the identity), the 8 x compressed-words
+ * bytes of x, and the byte '0' or '1' (the parity): 98, 194 (MNT4753 G2) or 290 (MNT6753 G2) bytes.  The identity is written as libff
+ * writes its zero() after to_affine_coordinates(), X = 0 and Y = 1: '1', zero bytes, '1'; both parity bytes are accepted for it on
+ * input, and it comes back as x all zero and flag 2.  A compressed proof is the three records A | B | C back to back (390 / 486
+ * bytes; r1cs_gg_ppzksnark_proof::operator<< where OUTPUT_NEWLINE is empty).
+ * to_stream: *len = the size; buf == NULL asks for the size alone; cap < *len, or a flag byte with a bit 2-7 set, is MNT753_EINVAL.
+ * from_stream: any other byte in a flag position, or len < n records, is MNT753_EINVAL. */
+int mnt753_points_to_stream(int curve, int group, const uint64_t* x, const uint8_t* flags, size_t n, uint8_t* buf, size_t cap, size_t* len);
+int mnt753_points_from_stream(int curve, int group, const uint8_t* buf, size_t len, size_t n, uint64_t* x, uint8_t* flags);
+
 /* ---- uniform scalars (host) ---------------------------------------------------------------------------
  * n elements of Fr of the curve, uniform in [0, r) by rejection on 753-bit draws of a seeded SplitMix64, in wire form.  What the
  * product needs them for: the scalars of the warm-up MSMs at parameter-load time (B::read_params) and the prover's second random

@@ -89,6 +89,14 @@ int mnt753_test_fold_parts(const mnt753_vk* vk, const uint64_t* proofs, const ui
  * [0] the scaling and the point sum, [1] the Miller loops and the products, [2] the tail (0 where it was skipped).  tools/bench_fold.py. */
 int mnt753_test_fold_last_timing(float out_ms[3]);
 
+/* The square root of csrc/fp_sqrt.hip.h on n raw field elements in wire form (host pointers): deg = 1 the base field Fq of the curve,
+ * deg = 2 (MNT4753) / 3 (MNT6753) the coordinate field of G2, c0 | c1 [| c2].  The lane mapping is the product's (k_decompress): one
+ * lane per base-field element, one lane group per extension element.  is_square[i] = 1 and out[i]^2 = in[i] (either root; 0 -> 0), or
+ * is_square[i] = 0 and out[i] = 0.  _window: the same with the window of the fixed exponent chosen (1, 2 or 4; the product's is
+ * SQRT_WINDOW) and, where ms is not NULL, the kernel's time on the device in milliseconds (HIP events; tools/bench_compress.py). */
+int mnt753_test_field_sqrt(int curve, int deg, const uint64_t* in_wire, size_t n, uint64_t* out_wire, uint8_t* is_square);
+int mnt753_test_field_sqrt_window(int curve, int deg, int window, const uint64_t* in_wire, size_t n, uint64_t* out_wire, uint8_t* is_square, float* ms);
+
 /* mnt753_vec_dot (op 0: a = dev_a, b = dev_b) or mnt753_poly_eval (op 1: coefficients dev_a, t = host_t, dev_b unused) with at most
  * max_blocks blocks of 256 threads in the reducing launch (0: the device's own cap), so that a test reaches the second grid-stride trip
  * of a thread at a small n: one block covers 256 elements of a dot and 256 * 16 coefficients of a polynomial.  Device pointers, the

@@ -206,6 +206,23 @@ public:
   };
   static folded_verdict verify_folded(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *proofs, const uint64_t *inputs, size_t n,
                                       const uint64_t *coefficients);
+  // Compressed points (mnt753_compress_points / mnt753_decompress_points / mnt753_groth16_verify_compressed):
+  // x and one flag byte per point -- bit 0 the parity of y as an integer, bit 1 the identity.  group: MNT753_G1 / MNT753_G2; wire words
+  // in host memory.  compress_points validates nothing; decompress_points reports like a check (entry "points"), a bad point's words
+  // are zero.  verify_compressed: x = n x (x_A | x_B | x_C), flags = n x 3; the verdicts of verify(), 1 also for a point that does not
+  // decompress and for an identity flag.
+  struct compressed_points {
+    std::vector<uint64_t> x;
+    std::vector<uint8_t> flags;
+  };
+  struct decompressed_points {
+    std::vector<uint64_t> affine;
+    check_entry report;
+  };
+  static compressed_points compress_points(int group, const uint64_t *affine, size_t n);
+  static decompressed_points decompress_points(int group, const uint64_t *x, const uint8_t *flags, size_t n);
+  static std::vector<uint8_t> verify_compressed(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *x, const uint8_t *flags, const uint64_t *inputs,
+                                                size_t n, bool check_subgroup);
   // raw access for tests / tools
   static const uint64_t *G1_words(const G1 *a);
   static const uint64_t *G2_words(const G2 *a);

@@ -194,6 +194,12 @@ def lib():
         "mnt753_groth16_verify": (i, [vp, vp, vp, sz, i, vp, vp]),
         "mnt753_groth16_verify_ex": (i, [vp, vp, vp, sz, i, C.c_uint, vp, vp]),
         "mnt753_groth16_verify_folded": (i, [vp, vp, vp, sz, i, u64p, vp, C.POINTER(C.c_int), vp]),
+        "mnt753_compressed_words": (sz, [i, i]),
+        "mnt753_compress_points": (i, [i, i, vp, i, sz, vp, vp, vp]),
+        "mnt753_decompress_points": (i, [i, i, vp, vp, i, sz, vp, C.POINTER(CheckReport), vp]),
+        "mnt753_groth16_verify_compressed": (i, [vp, vp, vp, vp, sz, i, C.c_uint, vp, vp]),
+        "mnt753_points_to_stream": (i, [i, i, vp, vp, sz, vp, sz, C.POINTER(C.c_size_t)]),
+        "mnt753_points_from_stream": (i, [i, i, vp, sz, sz, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL_SYMBOLS and not hasattr(L, name):
@@ -239,6 +245,8 @@ def test_lib():
         "mnt753_test_reduce_capped": (i, [i, i, C.c_void_p, C.c_void_p, sz, u64p, C.c_uint, u64p]),
         "mnt753_test_fold_parts": (i, [C.c_void_p, u64p, u64p, sz, u64p, u64p, u64p, u64p, u64p, C.c_void_p, C.POINTER(C.c_int)]),
         "mnt753_test_fold_last_timing": (i, [C.POINTER(C.c_float)]),
+        "mnt753_test_field_sqrt": (i, [i, i, u64p, sz, u64p, C.c_void_p]),
+        "mnt753_test_field_sqrt_window": (i, [i, i, i, u64p, sz, u64p, C.c_void_p, C.POINTER(C.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -684,6 +692,93 @@ def check_subgroup(curve, group, affine, on_device=False, n=None, stream=None):
     st = C.c_void_p(int(stream)) if stream else C.c_void_p()
     _check(lib().mnt753_check_subgroup(curve, group, ptr, 1 if on_device else 0, cnt, C.byref(rep), st), "mnt753_check_subgroup")
     return _report(rep)
+
+
+def compressed_words(curve, group):
+    return int(lib().mnt753_compressed_words(curve, group))
+
+
+def compress_points(curve, group, points, on_device=False, n=None, x_out=None, flags_out=None, stream=None):
+    """mnt753_compress_points: n affine wire points -> (x [n, compressed_words] uint64, flags [n] uint8: bit 0 the parity of y as an
+    integer (G2: of y.c0), bit 1 the identity).  Validates nothing.  on_device: points, x_out and flags_out are device addresses
+    (n given) and (x_out, flags_out) come back as they went in."""
+    ptr, cnt, keep = _input_ptr(points, on_device, affine_words(curve, group), n)
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    if on_device:
+        if x_out is None or flags_out is None:
+            raise Mnt753Error("compress_points: on_device needs the device addresses x_out and flags_out")
+        _check(lib().mnt753_compress_points(curve, group, ptr, 1, cnt, C.c_void_p(int(x_out)), C.c_void_p(int(flags_out)), st), "mnt753_compress_points")
+        return x_out, flags_out
+    x = np.zeros((cnt, compressed_words(curve, group)), dtype=np.uint64)
+    flags = np.zeros(cnt, dtype=np.uint8)
+    _check(lib().mnt753_compress_points(curve, group, ptr, 0, cnt, C.c_void_p(x.ctypes.data), C.c_void_p(flags.ctypes.data), st), "mnt753_compress_points")
+    return x, flags
+
+
+def decompress_points(curve, group, x, flags, on_device=False, n=None, out=None, stream=None):
+    """mnt753_decompress_points: (x, flags) -> (points [n, affine_words], (n_bad, first_bad, reason of first_bad: BAD_*)); a bad
+    point's words are zero, and so are the identity's.  on_device: x, flags and out are device addresses (n given) and out comes back
+    in place of the points."""
+    ptr, cnt, keep = _input_ptr(x, on_device, compressed_words(curve, group), n)
+    rep = CheckReport()
+    st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+    if on_device:
+        if out is None:
+            raise Mnt753Error("decompress_points: on_device needs the device address out")
+        _check(lib().mnt753_decompress_points(curve, group, ptr, C.c_void_p(int(flags)), 1, cnt, C.c_void_p(int(out)), C.byref(rep), st),
+               "mnt753_decompress_points")
+        return out, _report(rep)
+    fl = np.ascontiguousarray(flags, dtype=np.uint8)
+    if fl.size != cnt:
+        raise Mnt753Error("decompress_points: one flag byte per point")
+    pts = np.zeros((cnt, affine_words(curve, group)), dtype=np.uint64)
+    _check(lib().mnt753_decompress_points(curve, group, ptr, C.c_void_p(fl.ctypes.data), 0, cnt, C.c_void_p(pts.ctypes.data), C.byref(rep), st),
+           "mnt753_decompress_points")
+    return pts, _report(rep)
+
+
+def points_to_stream(curve, group, x, flags):
+    """mnt753_points_to_stream (host only): the packed compressed form -> libff's stream records, bytes"""
+    xs = np.ascontiguousarray(x, dtype=np.uint64)
+    fl = np.ascontiguousarray(flags, dtype=np.uint8)
+    n = fl.size
+    if xs.size != n * compressed_words(curve, group):
+        raise Mnt753Error("points_to_stream: one flag byte per point")
+    ln = C.c_size_t()
+    _check(lib().mnt753_points_to_stream(curve, group, C.c_void_p(xs.ctypes.data), C.c_void_p(fl.ctypes.data), n, None, 0, C.byref(ln)),
+           "mnt753_points_to_stream")
+    buf = np.zeros(max(ln.value, 1), dtype=np.uint8)
+    _check(lib().mnt753_points_to_stream(curve, group, C.c_void_p(xs.ctypes.data), C.c_void_p(fl.ctypes.data), n, C.c_void_p(buf.ctypes.data),
+                                         ln.value, C.byref(ln)), "mnt753_points_to_stream")
+    return buf[:ln.value].tobytes()
+
+
+def points_from_stream(curve, group, data, n=None):
+    """mnt753_points_from_stream (host only): n of libff's stream records (default: as many as data holds) -> (x, flags)"""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    rec = 8 * compressed_words(curve, group) + 2
+    cnt = buf.size // rec if n is None else int(n)
+    x = np.zeros((cnt, compressed_words(curve, group)), dtype=np.uint64)
+    flags = np.zeros(cnt, dtype=np.uint8)
+    _check(lib().mnt753_points_from_stream(curve, group, C.c_void_p(buf.ctypes.data) if buf.size else None, buf.size, cnt,
+                                           C.c_void_p(x.ctypes.data), C.c_void_p(flags.ctypes.data)), "mnt753_points_from_stream")
+    return x, flags
+
+
+def test_field_sqrt(curve, deg, elements, window=None):
+    """mnt753_test_field_sqrt[_window] (test library): n field elements [n, 12 deg] in wire form -> (roots [n, 12 deg], is_square [n]
+    uint8); window = 1, 2, 4 picks the window of the fixed exponent and also returns the kernel's milliseconds."""
+    a, pa = _u64(elements)
+    n = a.size // (12 * deg)
+    out = np.zeros((n, 12 * deg), dtype=np.uint64)
+    sq = np.zeros(n, dtype=np.uint8)
+    po = out.ctypes.data_as(C.POINTER(C.c_uint64))
+    if window is None:
+        _check(test_lib().mnt753_test_field_sqrt(curve, deg, pa, n, po, C.c_void_p(sq.ctypes.data)), "mnt753_test_field_sqrt")
+        return out, sq
+    ms = C.c_float(0)
+    _check(test_lib().mnt753_test_field_sqrt_window(curve, deg, window, pa, n, po, C.c_void_p(sq.ctypes.data), C.byref(ms)), "mnt753_test_field_sqrt_window")
+    return out, sq, float(ms.value)
 
 
 def check_scalars(curve, fr, on_device=False, n=None, stream=None):
@@ -1191,6 +1286,33 @@ class VerificationKey:
             rc = lib().mnt753_groth16_verify(self._h, pp, pi, cnt, 1 if on_device else 0, C.c_void_p(verdicts.ctypes.data), st)
         if rc < 0:
             _check(rc, "mnt753_groth16_verify")
+        return verdicts
+
+    def verify_compressed(self, x, flags, inputs, check_subgroup=False, on_device=False, n=None, stream=None):
+        """mnt753_groth16_verify_compressed.  x: n x (x_A | x_B | x_C) words, flags: n x 3 bytes (compress_points of A, B, C), inputs
+        as for verify() (numpy arrays, or device addresses with on_device and n) -> verdicts as verify(); 1 (malformed) also covers a
+        point that does not decompress and an identity flag."""
+        xw = 24 + compressed_words(self.curve, G2)
+        px, cnt, keep1 = _input_ptr(x, on_device, xw, n)
+        if on_device:
+            pf, keep3 = C.c_void_p(int(flags)), None
+        else:
+            keep3 = np.ascontiguousarray(flags, dtype=np.uint8)
+            if keep3.size != 3 * cnt:
+                raise Mnt753Error("verify_compressed: three flag bytes per proof")
+            pf = C.c_void_p(keep3.ctypes.data)
+        if self.num_inputs:
+            pi, cnt2, keep2 = _input_ptr(inputs, on_device, 12 * self.num_inputs, n)
+            if cnt2 != cnt:
+                raise Mnt753Error("verify_compressed: one row of inputs per proof")
+        else:
+            pi = C.c_void_p()
+        verdicts = np.zeros(cnt, dtype=np.uint8)
+        st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+        rc = lib().mnt753_groth16_verify_compressed(self._h, px, pf, pi, cnt, 1 if on_device else 0, VERIFY_CHECK_SUBGROUP if check_subgroup else 0,
+                                                    C.c_void_p(verdicts.ctypes.data), st)
+        if rc < 0:
+            _check(rc, "mnt753_groth16_verify_compressed")
         return verdicts
 
     def _fold_args(self, proofs, inputs, coefficients, on_device, n):

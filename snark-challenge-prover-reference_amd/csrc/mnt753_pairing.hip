@@ -5,6 +5,7 @@
 #include <cstring>
 #include <vector>
 #include "common_host.hpp"
+#include "compress_api.hpp"
 #include "mnt753_generators.h"
 #include "pairing_kernels.hip.h"
 #include "vk_object.hpp"
@@ -17,6 +18,15 @@ struct PairingBuffers {
   void *g1 = nullptr, *g2 = nullptr, *out = nullptr, *stand = nullptr, *ints = nullptr;
   ~PairingBuffers() {
     for (void* p : {g1, g2, out, stand, ints})
+      if (p) (void)hipFree(p);
+  }
+};
+
+// device memory of mnt753_groth16_verify_compressed beside those
+struct CompressedStage {
+  void *x = nullptr, *flags = nullptr, *rec = nullptr;
+  ~CompressedStage() {
+    for (void* p : {x, flags, rec})
       if (p) (void)hipFree(p);
   }
 };
@@ -264,9 +274,16 @@ int mnt753_groth16_verify(const mnt753_vk* vk, const uint64_t* proofs, const uin
   return mnt753_groth16_verify_ex(vk, proofs, inputs, n, on_device, 0u, verdicts, stream);
 }
 
-int mnt753_groth16_verify_ex(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int on_device, unsigned flags, uint8_t* verdicts,
-                             void* stream) {
-  if (!vk || (n && (!proofs || !verdicts || (vk->num_inputs && !inputs))) || n > MAX_PAIRINGS || (flags & ~MNT753_VERIFY_CHECK_SUBGROUP))
+namespace {
+// mnt753_groth16_verify_ex (cx == nullptr: proofs holds affine proofs) and mnt753_groth16_verify_compressed (cx, cflags: the packed
+// compressed proofs, n x (x_A | x_B | x_C) and n x 3 flag bytes; proofs unused): the same chunks, buffers and kernels, with a chunk of
+// compressed proofs decompressed into the affine staging buffer first.  A point that does not decompress, and an identity flag, leave
+// zero words there, which the verifier reads as the identity: verdict 1.
+int verify_chunks(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* cx, const uint8_t* cflags, const uint64_t* inputs, size_t n, int on_device,
+                  unsigned flags, uint8_t* verdicts, void* stream) {
+  const bool compressed = cx != nullptr;
+  if (!vk || (n && ((!compressed && !proofs) || (compressed && !cflags) || !verdicts || (vk->num_inputs && !inputs))) || n > MAX_PAIRINGS ||
+      (flags & ~MNT753_VERIFY_CHECK_SUBGROUP))
     return set_error(MNT753_EINVAL, "groth16_verify: bad argument");
   const bool sub = (flags & MNT753_VERIFY_CHECK_SUBGROUP) != 0;
   if (int rc = require_device()) return rc;
@@ -274,17 +291,31 @@ int mnt753_groth16_verify_ex(const mnt753_vk* vk, const uint64_t* proofs, const 
   OnDevice guard(vk->device);
   hipStream_t st = (hipStream_t)stream;
   const size_t ni = vk->num_inputs, w2 = mnt753_affine_words(vk->curve, MNT753_G2), pw = 48 + w2;   // words of one proof
-  if (on_device && (!on_device_of(proofs, vk->device) || (ni && !on_device_of(inputs, vk->device))))
+  const size_t xw = 24 + w2 / 2;                  // words of one compressed proof
+  if (on_device && (!on_device_of(compressed ? (const void*)cx : (const void*)proofs, vk->device) || (compressed && !on_device_of(cflags, vk->device)) ||
+                    (ni && !on_device_of(inputs, vk->device))))
     return set_error(MNT753_EINVAL, "groth16_verify: proofs and inputs must lie on the device of the key");
   // what one proof of a chunk takes: the accumulated point, the inputs as integers, flag and verdict, and its staged copy if it
-  // arrives in host memory.  The cap of the key bounds the chunk (at least one proof, at most 2^16).
-  const size_t per_proof = 194 + 96 * ni + (on_device ? 0 : 8 * pw + 96 * ni);
+  // arrives in host memory; a compressed proof: its decompressed words as well.  The cap of the key bounds the chunk (at least one
+  // proof, at most 2^16).
+  const size_t per_proof = 194 + 96 * ni + (compressed ? 8 * pw : 0) + (on_device ? 0 : (compressed ? 8 * xw + 3 : 8 * pw) + 96 * ni);
   size_t chunk = n < VERIFY_CHUNK ? n : VERIFY_CHUNK;
   if (vk->workspace_cap && vk->workspace_cap / per_proof < chunk) chunk = vk->workspace_cap / per_proof ? vk->workspace_cap / per_proof : 1;
-  PairingBuffers buf;   // g1: staged proofs, g2: staged inputs, out: accumulated points, stand: flags then verdicts, ints: inputs as integers
-  if (!on_device) {
+  PairingBuffers buf;   // g1: staged (or decompressed) proofs, g2: staged inputs, out: accumulated points, stand: flags then verdicts, ints: inputs as integers
+  CompressedStage cs;   // the staged compressed proofs of a host batch, and the record of the decompression (not read: the verdicts tell)
+  if (!on_device || compressed) {
     if (int rc = alloc(&buf.g1, 8 * pw * chunk)) return rc;
+  }
+  if (!on_device) {
     if (ni) { if (int rc = alloc(&buf.g2, 96 * ni * chunk)) return rc; }
+  }
+  if (compressed) {
+    if (!on_device) {
+      if (int rc = alloc(&cs.x, 8 * xw * chunk)) return rc;
+      if (int rc = alloc(&cs.flags, 3 * chunk)) return rc;
+    }
+    if (int rc = alloc(&cs.rec, decompress_report_bytes())) return rc;
+    if (int rc = decompress_report_init(cs.rec, st)) return rc;
   }
   if (ni) { if (int rc = alloc(&buf.ints, 96 * ni * chunk)) return rc; }
   if (int rc = alloc(&buf.out, 192 * chunk)) return rc;
@@ -294,11 +325,30 @@ int mnt753_groth16_verify_ex(const mnt753_vk* vk, const uint64_t* proofs, const 
   size_t rejected = 0;
   for (size_t first = 0; first < n; first += chunk) {
     const size_t cnt = n - first < chunk ? n - first : chunk;
-    const uint64_t* dp = proofs + first * pw;
+    const uint64_t* dp = compressed ? nullptr : proofs + first * pw;
     const uint64_t* di = ni ? inputs + first * ni * 12 : nullptr;
-    if (!on_device) {
-      HIP_TRY(hipMemcpyAsync(buf.g1, dp, 8 * pw * cnt, hipMemcpyHostToDevice, st));
+    if (compressed) {
+      const uint64_t* dx = cx + first * xw;
+      const uint8_t* df = cflags + first * 3;
+      if (!on_device) {
+        HIP_TRY(hipMemcpyAsync(cs.x, dx, 8 * xw * cnt, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(cs.flags, df, 3 * cnt, hipMemcpyHostToDevice, st));
+        dx = reinterpret_cast<const uint64_t*>(cs.x);
+        df = reinterpret_cast<const uint8_t*>(cs.flags);
+      }
+      // A, B, C of every proof into its A | B | C row; the stand-in x: the generators at the head of the key
+      const uint32_t *x32 = reinterpret_cast<const uint32_t*>(dx), *key32 = reinterpret_cast<const uint32_t*>(vk->dev_key);
+      uint32_t* o32 = reinterpret_cast<uint32_t*>(buf.g1);
+      if (int rc = decompress_enqueue(vk->curve, MNT753_G1, x32, 2 * xw, df, 3, key32, o32, 2 * pw, cnt, first, cs.rec, st)) return rc;
+      if (int rc = decompress_enqueue(vk->curve, MNT753_G2, x32 + 24, 2 * xw, df + 1, 3, key32 + 48, o32 + 48, 2 * pw, cnt, first, cs.rec, st)) return rc;
+      if (int rc = decompress_enqueue(vk->curve, MNT753_G1, x32 + 24 + w2, 2 * xw, df + 2, 3, key32, o32 + 48 + 2 * w2, 2 * pw, cnt, first, cs.rec, st)) return rc;
       dp = reinterpret_cast<const uint64_t*>(buf.g1);
+    }
+    if (!on_device) {
+      if (!compressed) {
+        HIP_TRY(hipMemcpyAsync(buf.g1, dp, 8 * pw * cnt, hipMemcpyHostToDevice, st));
+        dp = reinterpret_cast<const uint64_t*>(buf.g1);
+      }
       if (ni) {
         HIP_TRY(hipMemcpyAsync(buf.g2, di, 96 * ni * cnt, hipMemcpyHostToDevice, st));
         di = reinterpret_cast<const uint64_t*>(buf.g2);
@@ -322,6 +372,22 @@ int mnt753_groth16_verify_ex(const mnt753_vk* vk, const uint64_t* proofs, const 
     for (size_t k = 0; k < cnt; ++k) rejected += verdicts[first + k] != 0;
   }
   return (int)rejected;
+}
+}  // namespace
+
+int mnt753_groth16_verify_ex(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int on_device, unsigned flags, uint8_t* verdicts,
+                             void* stream) {
+  return verify_chunks(vk, proofs, nullptr, nullptr, inputs, n, on_device, flags, verdicts, stream);
+}
+
+int mnt753_groth16_verify_compressed(const mnt753_vk* vk, const uint64_t* x, const uint8_t* flags, const uint64_t* inputs, size_t n, int on_device,
+                                     unsigned verify_flags, uint8_t* verdicts, void* stream) {
+  if (n && !x) return set_error(MNT753_EINVAL, "groth16_verify_compressed: bad argument");
+  if (!n) {                                        // (verify_chunks tells the forms apart by x)
+    if (!vk || (verify_flags & ~MNT753_VERIFY_CHECK_SUBGROUP)) return set_error(MNT753_EINVAL, "groth16_verify_compressed: bad argument");
+    return require_device();
+  }
+  return verify_chunks(vk, nullptr, x, flags, inputs, n, on_device, verify_flags, verdicts, stream);
 }
 
 // Subgroup membership of n points.  G1 has cofactor 1 on both curves: mnt753_check_points' record is the answer.  G2: k_g2_subgroup,

@@ -1,6 +1,6 @@
 // ./main_hip <curve> <command> ...     <curve>: MNT4753 | MNT6753
 // The commands are the rows of `commands` near the end of this file, in that order: compute, compute-r1cs, complete, check, check-r1cs,
-// qap-at, generate, vk, verify, self-test.  Each row carries its usage text, which names the command's words and options and is what
+// qap-at, generate, vk, verify, compress-proof, decompress-proof, self-test.  Each row carries its usage text, which names the command's words and options and is what
 // the program prints for a command line it cannot read; the comment above each command's function says what the command does.
 // Options come from, in rising precedence: defaults, the environment (read_environment), the command line.
 // Exit codes: 0 success, 1 device / I/O / self-test failure, 2 usage, 3 an input failed validation (or its H failed --check-h).
@@ -611,7 +611,90 @@ static bool fold_coefficients(const char* path, size_t n, std::vector<uint64_t>&
       if (getrandom(&out[2 * k], 16, 0) != 16) { fprintf(stderr, "main_hip: getrandom failed\n"); return false; }
   return true;
 }
-struct VerifyOptions { bool check_subgroup = false, fold = false; const char* fold_file = nullptr; };
+struct VerifyOptions { bool check_subgroup = false, fold = false, compressed = false; const char* fold_file = nullptr; };
+
+// ---- compressed proofs: libff's stream of A | B | C with point compression on, 390 (MNT4753) or 486 (MNT6753) bytes ----
+// the records of a proof: group and words of x, in the order of the file
+struct ProofPart { const char* name; int group; size_t xw; };
+static std::vector<ProofPart> proof_parts(int curve) {
+  return {{"A", MNT753_G1, 12}, {"B", MNT753_G2, mnt753_compressed_words(curve, MNT753_G2)}, {"C", MNT753_G1, 12}};
+}
+static size_t proof_stream_bytes(int curve) { return 3 * 2 + 8 * (24 + mnt753_compressed_words(curve, MNT753_G2)); }
+// the stream of one proof -> its packed form x_A | x_B | x_C and three flag bytes; false (with the line on stderr) for a file that is
+// no such stream
+static bool read_proof_stream(int curve, const char* path, uint64_t* x, uint8_t* flags) {
+  std::vector<uint8_t> bytes(proof_stream_bytes(curve));
+  const std::string wrong = std::string(path) + " is not a compressed proof (" + std::to_string(bytes.size()) + " bytes)";
+  if (!read_exact(path, bytes.data(), bytes.size(), true, std::string("cannot open ") + path, wrong)) return false;
+  size_t at = 0, k = 0;
+  for (const ProofPart& p : proof_parts(curve)) {
+    if (mnt753_points_from_stream(curve, p.group, bytes.data() + at, 8 * p.xw + 2, 1, x, flags + k) != 0) {
+      fprintf(stderr, "main_hip: %s: %s: %s\n", path, p.name, mnt753_last_error());
+      return false;
+    }
+    at += 8 * p.xw + 2; x += p.xw; ++k;
+  }
+  return true;
+}
+// `main_hip <curve> compress-proof <proof> <out>`: A | B | C in wire words -> the stream.  Validates nothing, like libff's operator<<.
+template <typename B>
+static int compress_proof(int curve, const char* in_path, const char* out_path) {
+  const size_t w2 = mnt753_affine_words(curve, MNT753_G2);
+  std::vector<uint64_t> proof(48 + w2);
+  const std::string wrong = std::string(in_path) + " is not a proof A | B | C";
+  if (!read_exact(in_path, proof.data(), 8 * proof.size(), true, std::string("cannot open ") + in_path, wrong)) return 1;
+  if (mnt753_init(0) != 0) { fprintf(stderr, "main_hip: %s\n", mnt753_last_error()); return 1; }
+  std::vector<uint8_t> out(proof_stream_bytes(curve));
+  size_t at = 0, from = 0;
+  for (const ProofPart& p : proof_parts(curve)) {
+    const auto c = B::compress_points(p.group, proof.data() + from, 1);
+    size_t len = 0;
+    ck(mnt753_points_to_stream(curve, p.group, c.x.data(), c.flags.data(), 1, out.data() + at, out.size() - at, &len), "mnt753_points_to_stream");
+    at += len; from += 2 * p.xw;
+  }
+  const std::string cannot_write = std::string("cannot write ") + out_path;
+  return write_file(out_path, {{out.data(), out.size()}}, cannot_write, cannot_write) ? 0 : 1;
+}
+// `main_hip <curve> decompress-proof <in> <out>`: the stream -> A | B | C in wire words; a record that is not a point ("A: off curve",
+// "B: not canonical") or a file that is no stream: exit 3, nothing written
+template <typename B>
+static int decompress_proof(int curve, const char* in_path, const char* out_path) {
+  std::vector<uint64_t> x(24 + mnt753_compressed_words(curve, MNT753_G2));
+  uint8_t flags[3];
+  if (!read_proof_stream(curve, in_path, x.data(), flags)) return 3;
+  if (mnt753_init(0) != 0) { fprintf(stderr, "main_hip: %s\n", mnt753_last_error()); return 1; }
+  std::vector<uint64_t> proof;
+  size_t from = 0, k = 0;
+  bool ok = true;
+  for (const ProofPart& p : proof_parts(curve)) {
+    const auto d = B::decompress_points(p.group, x.data() + from, flags + k, 1);
+    if (d.report.n_bad) { fprintf(stderr, "main_hip: %s: %s: %s\n", in_path, p.name, B::check_reason_text(d.report.reason)); ok = false; }
+    proof.insert(proof.end(), d.affine.begin(), d.affine.end());
+    from += p.xw; ++k;
+  }
+  if (!ok) return 3;
+  const std::string cannot_write = std::string("cannot write ") + out_path;
+  return write_file(out_path, {{proof.data(), 8 * proof.size()}}, cannot_write, cannot_write) ? 0 : 1;
+}
+// verify --compressed: the proof files are streams; a proof that does not decompress prints REJECTED (malformed)
+template <typename B>
+static int verify_compressed_batch(const VerifyOptions& vo, const std::vector<uint64_t>& el, size_t num_inputs, const std::vector<uint64_t>& x,
+                                   const std::vector<uint8_t>& flags, const std::vector<uint64_t>& per_proof, size_t n) {
+  if (vo.check_subgroup) {
+    const auto e = B::check_subgroup(el.data() + 24, 2);
+    if (e.n_bad) {
+      fprintf(stderr, "main_hip: %s of the key: %s\n", e.first_bad == 0 ? "beta_g2" : "delta_g2", B::check_reason_text(e.reason));
+      return 3;
+    }
+  }
+  const std::vector<uint8_t> verdicts = B::verify_compressed(el.data(), num_inputs, x.data(), flags.data(), per_proof.data(), n, vo.check_subgroup);
+  int bad = 0;
+  for (size_t k = 0; k < n; ++k) {
+    printf("%s\n", verdicts[k] == 0 ? "VERIFIED" : (verdicts[k] == 3 ? "REJECTED (B not in the subgroup)" : (verdicts[k] == 1 ? "REJECTED (malformed)" : "REJECTED")));
+    bad += verdicts[k] != 0;
+  }
+  return bad ? 3 : 0;
+}
 // through the wrapper class, as a C++ caller would: B::verify makes the key, verifies the batch and drops the key
 template <typename B>
 static int verify_batch(const VerifyOptions& vo, const std::vector<uint64_t>& el, size_t num_inputs, const std::vector<uint64_t>& proofs,
@@ -649,6 +732,17 @@ static int verify_proofs(int curve, const std::vector<const char*>& pos, const V
   // the leading element is the constant 1: R mod r, the Montgomery one of Fr (modulus A on MNT4753, B on MNT6753)
   if (memcmp(inputs.data(), mnt753::FPC[curve].one64, 96) != 0) { fprintf(stderr, "main_hip: %s does not start with the constant 1\n", pos[1]); return 3; }
   const size_t n = pos.size() - 2;
+  if (vo.compressed) {
+    const size_t xw = 24 + mnt753_compressed_words(curve, MNT753_G2);
+    std::vector<uint64_t> x(n * xw);
+    std::vector<uint8_t> flags(3 * n);
+    for (size_t k = 0; k < n; ++k)
+      if (!read_proof_stream(curve, pos[k + 2], x.data() + k * xw, flags.data() + 3 * k)) return 3;
+    if (mnt753_init(0) != 0) { fprintf(stderr, "main_hip: %s\n", mnt753_last_error()); return 1; }
+    std::vector<uint64_t> rows;
+    for (size_t k = 0; k < n; ++k) rows.insert(rows.end(), inputs.begin() + 12, inputs.end());
+    return with_curve(curve, [&](auto b) { return verify_compressed_batch<decltype(b)>(vo, el, num_inputs, x, flags, rows, n); });
+  }
   for (size_t k = 2; k < pos.size(); ++k) {
     std::vector<uint64_t> one;
     if (!read_all_words(pos[k], one)) return 1;
@@ -736,6 +830,7 @@ static int qap_at_command(const Command&, Options&, int, char**);
 static int generate_command(const Command&, Options&, int, char**);
 static int vk_command(const Command&, Options&, int, char**);
 static int self_test_command(const Command&, Options&, int, char**);
+static int proof_stream_command(const Command&, Options&, int, char**);
 
 // also what a command line too short to name its files gets, whatever its command word
 static const char compute_usage[] =
@@ -754,7 +849,13 @@ static const char vk_usage[] =
     "  --check-subgroup: beta_g2 and delta_g2 of the key and B of every proof must lie in G2, the order-r subgroup of the twist;\n"
     "    a key that fails is named and nothing is verified (exit 3), such a proof prints REJECTED (B not in the subgroup).\n"
     "  --fold: the batch under one final exponentiation first (random coefficients, or n x 16 bytes from --fold-coefficients);\n"
-    "    accepted: one line naming the count, exit 0; rejected: the per-proof lines of --check-subgroup, exit 3.\n";
+    "    accepted: one line naming the count, exit 0; rejected: the per-proof lines of --check-subgroup, exit 3.\n"
+    "  --compressed: the proof files are libff's compressed streams (compress-proof); a proof that does not decompress prints\n"
+    "    REJECTED (malformed).  Not with --fold.\n";
+static const char proof_stream_usage[] =
+    "usage: %s MNT4753|MNT6753 compress-proof <proof> <out>\n       %s MNT4753|MNT6753 decompress-proof <in> <out>\n"
+    "  compress-proof: A | B | C in wire words -> libff's stream with point compression on (390 / 486 bytes); validates nothing.\n"
+    "  decompress-proof: the reverse; a record that is no point of its curve is named (\"B: off curve\"), exit code 3, nothing is written.\n";
 static const Command commands[] = {
     {"compute", prove_command, false, compute_usage},
     {"compute-r1cs", prove_command, true, "usage: %s <curve> compute-r1cs <params> <r1cs> <witness> <output>\n"},
@@ -771,6 +872,8 @@ static const Command commands[] = {
      "  operating system's generator and written nowhere, and the G1 generator is the curve's standard one.\n"},
     {"vk", vk_command, false, vk_usage},
     {"verify", vk_command, true, vk_usage},
+    {"compress-proof", proof_stream_command, false, proof_stream_usage},
+    {"decompress-proof", proof_stream_command, true, proof_stream_usage},
     {"self-test", self_test_command, false, nullptr},   // takes no words
 };
 // A word that is no command (and `complete` short of its paths) has always been read as compute's line and refused only behind its
@@ -906,19 +1009,35 @@ static int vk_command(const Command& self, Options&, int argc, char** argv) {
   const int curve = parse_curve(argv[1]);
   if (curve < 0) return unknown_curve(argv[1]);
   std::vector<Flag> flags;
-  if (verify) flags = {{"--check-subgroup", false}, {"--fold", false}, {"--fold-coefficients", true}};
+  if (verify) flags = {{"--check-subgroup", false}, {"--fold", false}, {"--fold-coefficients", true}, {"--compressed", false}};
   ArgScan a{argc, argv, 3, flags};
   std::vector<const char*> pos;
   VerifyOptions vo;
   while (a.next()) {
     if (a.is("--check-subgroup")) vo.check_subgroup = true;
+    else if (a.is("--compressed")) vo.compressed = true;
     else if (a.is("--fold")) vo.fold = vo.check_subgroup = true;
     else if (a.is("--fold-coefficients")) vo.fold_file = a.value;
     else pos.push_back(a.value);
   }
   if (a.refused) return 2;
   if (verify ? pos.size() < 3 : pos.size() != 2) return usage(self.usage, argv[0]);
+  if (vo.compressed && vo.fold) { fprintf(stderr, "main_hip: --fold takes no compressed proofs\n"); return 2; }
   return vk_or_verify(curve, verify, pos, vo);
+}
+
+// compress-proof <proof> <out> and decompress-proof <in> <out>
+static int proof_stream_command(const Command& self, Options&, int argc, char** argv) {
+  const int curve = parse_curve(argv[1]);
+  if (curve < 0) return unknown_curve(argv[1]);
+  ArgScan a{argc, argv, 3, {}};
+  std::vector<const char*> pos;
+  while (a.next()) pos.push_back(a.value);
+  if (a.refused) return 2;
+  if (pos.size() != 2) return usage(self.usage, argv[0]);
+  return with_curve(curve, [&](auto b) {
+    return self.second_form ? decompress_proof<decltype(b)>(curve, pos[0], pos[1]) : compress_proof<decltype(b)>(curve, pos[0], pos[1]);
+  });
 }
 
 // `main_hip <curve> self-test`: the known-answer checks of this build at their widest (level 2: also over window tables)

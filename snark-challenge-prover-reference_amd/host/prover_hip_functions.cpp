@@ -1500,6 +1500,29 @@ template <int CURVE> typename HIP_B::folded_verdict HIP_B::verify_folded(const u
   out.accepted = accepted != 0;
   return out;
 }
+template <int CURVE> typename HIP_B::compressed_points HIP_B::compress_points(int group, const uint64_t* affine, size_t n) {
+  compressed_points out{std::vector<uint64_t>(n * mnt753_compressed_words(CURVE, group)), std::vector<uint8_t>(n)};
+  check(mnt753_compress_points(CURVE, group, affine, 0, n, out.x.data(), out.flags.data(), nullptr), "mnt753_compress_points");
+  return out;
+}
+template <int CURVE> typename HIP_B::decompressed_points HIP_B::decompress_points(int group, const uint64_t* x, const uint8_t* flags, size_t n) {
+  decompressed_points out{std::vector<uint64_t>(n * mnt753_affine_words(CURVE, group)), {}};
+  mnt753_check_report r;
+  check(mnt753_decompress_points(CURVE, group, x, flags, 0, n, out.affine.data(), &r, nullptr), "mnt753_decompress_points");
+  out.report = {"points", n, r.n_bad, r.first_bad, (int)r.first_reason};
+  return out;
+}
+template <int CURVE> std::vector<uint8_t> HIP_B::verify_compressed(const uint64_t* vk_elements, size_t num_inputs, const uint64_t* x, const uint8_t* flags,
+                                                                   const uint64_t* inputs, size_t n, bool check_subgroup) {
+  const size_t w2 = mnt753_affine_words(CURVE, MNT753_G2);
+  mnt753_vk* vk = nullptr;
+  check(mnt753_vk_create(CURVE, vk_elements, vk_elements + 24, vk_elements + 24 + w2, vk_elements + 24 + 2 * w2, num_inputs, &vk), "mnt753_vk_create");
+  std::vector<uint8_t> verdicts(n);
+  const int rc = mnt753_groth16_verify_compressed(vk, x, flags, inputs, n, 0, check_subgroup ? MNT753_VERIFY_CHECK_SUBGROUP : 0u, verdicts.data(), nullptr);
+  mnt753_vk_destroy(vk);
+  if (rc < 0) check(rc, "mnt753_groth16_verify_compressed");
+  return verdicts;
+}
 
 template class mnt753_hip_impl<0>;
 template class mnt753_hip_impl<1>;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Derive every numeric table the HIP field layer needs from the two MNT753 primes.
 
-Writes snark-challenge-prover-reference_amd/csrc/mnt753_constants.h and mnt753_pairing_constants.h (committed; regenerate
+Writes snark-challenge-prover-reference_amd/csrc/mnt753_constants.h, mnt753_pairing_constants.h and mnt753_sqrt_constants.h (committed; regenerate
 with `python tools/gen_constants.py`).  Inputs are the decimal literals in tools/mnt753_params.py,
 which cite the reference's curve-initialisation files line by line.
 
@@ -174,6 +174,79 @@ def emit_pairing():
     print("wrote", os.path.normpath(path))
 
 
+def sqrt_constants(q, deg, nr):
+    """Tonelli-Shanks constants of F = Fq[u] / (u^deg - nr) (deg 1: Fq itself): q^deg - 1 = 2^s t with t odd, the exponent (t - 1) / 2,
+    and z^t for the first non-square z of a fixed walk (small integers, then u, u + 1, ...).  All asserted: z^((q^deg - 1) / 2) = -1,
+    z^t has order exactly 2^s."""
+    def mul(x, y):
+        out = [0] * (2 * deg - 1)
+        for i in range(deg):
+            for j in range(deg):
+                out[i + j] += x[i] * y[j]
+        for k in range(2 * deg - 2, deg - 1, -1):
+            out[k - deg] += nr * out[k]
+        return tuple(v % q for v in out[:deg])
+
+    def fpow(x, e):
+        acc = (1,) + (0,) * (deg - 1)
+        for bit in bin(e)[2:]:
+            acc = mul(acc, acc)
+            if bit == "1":
+                acc = mul(acc, x)
+        return acc
+    order = q ** deg - 1
+    s = (order & -order).bit_length() - 1
+    t = order >> s
+    one, minus_one = (1,) + (0,) * (deg - 1), (q - 1,) + (0,) * (deg - 1)
+    walk = [(v,) + (0,) * (deg - 1) for v in range(2, 40)]
+    if deg > 1:
+        walk = [(v, 1) + (0,) * (deg - 2) for v in range(0, 40)] + walk
+    z = next(c for c in walk if fpow(c, order // 2) == minus_one)
+    zt = fpow(z, t)
+    assert fpow(zt, 1 << (s - 1)) == minus_one and fpow(zt, 1 << s) == one
+    return {"s": s, "e": (t - 1) // 2, "z": z, "zt": zt}
+
+
+SQRT_WORDS = 70   # 32-bit words of the longest exponent: (t - 1) / 2 of Fq3 has 2229 bits
+
+
+def emit_sqrt():
+    """csrc/mnt753_sqrt_constants.h: the square-root constants of the four coordinate fields (csrc/fp_sqrt.hip.h)."""
+    A, B = P.MOD_A, P.MOD_B
+    rp = 1 << RP_BITS
+    fields = (("Fq of MNT4753", B, 1, 0), ("Fq of MNT6753", A, 1, 0),
+              ("Fq2 of MNT4753", B, 2, P.MNT4_FQ2_NON_RESIDUE), ("Fq3 of MNT6753", A, 3, P.MNT6_FQ3_NON_RESIDUE))
+    out = []
+    out.append("// GENERATED by tools/gen_constants.py -- do not edit.  Tonelli-Shanks constants of the four coordinate fields, from the two moduli")
+    out.append("// of tools/mnt753_params.py: with |F| - 1 = 2^s t, t odd, the exponent (t - 1) / 2 and z^t for a non-square z (csrc/fp_sqrt.hip.h).")
+    out.append("#pragma once")
+    out.append("#include <stdint.h>")
+    out.append('#include "mnt753_constants.h"')
+    out.append("namespace mnt753 {")
+    out.append("struct SqrtConst {")
+    out.append("  int s;                     // 2-adicity of |F| - 1")
+    out.append("  int e_bits;                // bit length of (t - 1) / 2")
+    out.append("  uint32_t e[%d];            // (t - 1) / 2, 32-bit words, little endian" % SQRT_WORDS)
+    out.append("  uint32_t zt[3][NL];        // z^t per component, device form; unused components zero")
+    out.append("};")
+    out.append("// index: 0 Fq of MNT4753, 1 Fq of MNT6753, 2 Fq2 of MNT4753, 3 Fq3 of MNT6753")
+    out.append("static constexpr SqrtConst SQRTC[4] = {")
+    for k, (name, q, deg, nr) in enumerate(fields):
+        c = sqrt_constants(q, deg, nr)
+        zt = list(c["zt"]) + [0] * (3 - deg)
+        s = "  { /* %s: z = %s */\n" % (name, "(" + ", ".join(str(v) for v in c["z"]) + ")")
+        s += "    %d, %d,\n    %s,\n    {" % (c["s"], c["e"].bit_length(), arr(limbs(c["e"], SQRT_WORDS, 32)))
+        s += ",\n     ".join(arr(limbs(v * rp % q, NL, LB), 7) for v in zt) + "}\n  }" + ("," if k < 3 else "")
+        out.append(s)
+    out.append("};")
+    out.append("}  // namespace mnt753")
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
+                        "snark-challenge-prover-reference_amd", "csrc", "mnt753_sqrt_constants.h")
+    with open(path, "w") as f:
+        f.write("\n".join(out) + "\n")
+    print("wrote", os.path.normpath(path))
+
+
 def main():
     A, B = P.MOD_A, P.MOD_B
     dA, dB = fp_const(A), fp_const(B)
@@ -259,6 +332,7 @@ def main():
         f.write("\n".join(o) + "\n")
     print("wrote", os.path.normpath(opath))
     emit_pairing()
+    emit_sqrt()
 
 
 if __name__ == "__main__":

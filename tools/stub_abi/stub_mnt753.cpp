@@ -14,6 +14,7 @@
 
 #include "../../include/mnt753_hip.h"
 #include "../../snark-challenge-prover-reference_amd/csrc/host_field.hpp"
+#include "../../snark-challenge-prover-reference_amd/csrc/point_stream.hpp"
 
 using namespace mnt753;
 using namespace mnt753::host;
@@ -323,6 +324,62 @@ int mnt753_groth16_verify_ex(const mnt753_vk* vk, const uint64_t* proofs, const 
 }
 int mnt753_groth16_verify(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int od, uint8_t* verdicts, void* st) {
   return mnt753_groth16_verify_ex(vk, proofs, inputs, n, od, 0u, verdicts, st);
+}
+// compressed points: no arithmetic -- compress copies x and gives flag 0 (2 for y = 0), decompress copies x back and writes y = x
+// (a point whose words are not zero); MNT753_STUB_BAD_POINT=<index> makes that element of a long enough set BAD_OFF_CURVE, as in
+// mnt753_check_points.  The stream records are the product's own codec (csrc/point_stream.hpp: bytes only).
+size_t mnt753_compressed_words(int curve, int group) { return bad_cg(curve, group) ? 0 : mnt753_affine_words(curve, group) / 2; }
+int mnt753_compress_points(int curve, int group, const uint64_t* aff, int, size_t n, uint64_t* x, uint8_t* flags, void*) {
+  if (bad_cg(curve, group) || (n && (!aff || !x || !flags))) return fail(MNT753_EINVAL, "compress_points: bad argument");
+  if (!g_ndev) return fail(MNT753_ENODEV, "no device");
+  const size_t wx = mnt753_compressed_words(curve, group);
+  for (size_t i = 0; i < n; ++i) {
+    uint64_t yor = 0;
+    for (size_t k = 0; k < wx; ++k) yor |= aff[(2 * i + 1) * wx + k];
+    for (size_t k = 0; k < wx; ++k) x[i * wx + k] = yor ? aff[2 * i * wx + k] : 0;
+    flags[i] = yor ? 0 : 2;
+  }
+  return 0;
+}
+int mnt753_decompress_points(int curve, int group, const uint64_t* x, const uint8_t* flags, int, size_t n, uint64_t* aff, mnt753_check_report* out, void*) {
+  if (bad_cg(curve, group) || !out || (n && (!x || !flags || !aff))) return fail(MNT753_EINVAL, "decompress_points: bad argument");
+  if (!g_ndev) return fail(MNT753_ENODEV, "no device");
+  const size_t wx = mnt753_compressed_words(curve, group);
+  *out = mnt753_check_report{0, 0, MNT753_BAD_NONE, 0};
+  stub_report(out, "MNT753_STUB_BAD_POINT", n, MNT753_BAD_OFF_CURVE);
+  for (size_t i = 0; i < n; ++i) {
+    const bool zero = (flags[i] & 2u) || (out->n_bad && out->first_bad == i);
+    for (size_t k = 0; k < wx; ++k) aff[2 * i * wx + k] = aff[(2 * i + 1) * wx + k] = zero ? 0 : (x[i * wx + k] | 1u);
+  }
+  return 0;
+}
+int mnt753_groth16_verify_compressed(const mnt753_vk* vk, const uint64_t* x, const uint8_t* flags, const uint64_t* inputs, size_t n, int od, unsigned vflags,
+                                     uint8_t* verdicts, void* st) {
+  if (!vk || (n && (!x || !flags || !verdicts)) || (vflags & ~MNT753_VERIFY_CHECK_SUBGROUP)) return fail(MNT753_EINVAL, "groth16_verify_compressed: bad argument");
+  const size_t xw = 24 + mnt753_compressed_words(vk->curve, MNT753_G2);
+  touch_ro(x, n * xw);
+  std::string proofs(8 * n * (48 + mnt753_affine_words(vk->curve, MNT753_G2)) + 8, '\1');   // what a decompressed batch would be
+  int rc = mnt753_groth16_verify_ex(vk, reinterpret_cast<const uint64_t*>(proofs.data()), inputs, n, od, vflags, verdicts, st);
+  if (rc < 0) return rc;
+  rc = 0;
+  for (size_t i = 0; i < n; ++i) {               // an identity flag or an unknown flag bit on A, B or C: malformed
+    if ((flags[3 * i] | flags[3 * i + 1] | flags[3 * i + 2]) & 0xfeu) verdicts[i] = 1;
+    rc += verdicts[i] != 0;
+  }
+  return rc;
+}
+int mnt753_points_to_stream(int curve, int group, const uint64_t* x, const uint8_t* flags, size_t n, uint8_t* buf, size_t cap, size_t* len) {
+  if (bad_cg(curve, group) || !len || (n && (!x || !flags))) return fail(MNT753_EINVAL, "points_to_stream: bad argument");
+  const size_t xb = 8 * mnt753_compressed_words(curve, group);
+  *len = n * (xb + 2);
+  if (!buf) return 0;
+  if (cap < *len) return fail(MNT753_EINVAL, "points_to_stream: buffer too small");
+  return stream_write(xb, x, flags, n, buf) == STREAM_OK ? 0 : fail(MNT753_EINVAL, "points_to_stream: a flag byte has a bit above the identity flag set");
+}
+int mnt753_points_from_stream(int curve, int group, const uint8_t* buf, size_t len, size_t n, uint64_t* x, uint8_t* flags) {
+  if (bad_cg(curve, group) || (n && (!buf || !x || !flags))) return fail(MNT753_EINVAL, "points_from_stream: bad argument");
+  return stream_read(8 * mnt753_compressed_words(curve, group), buf, len, n, x, flags) == STREAM_OK
+             ? 0 : fail(MNT753_EINVAL, "points_from_stream: not n well-formed records");
 }
 // MNT753_STUB_REJECT rejects the fold as it rejects every proof
 int mnt753_groth16_verify_folded(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int, const uint64_t* coefficients, uint8_t* status,
