@@ -523,8 +523,39 @@ int mnt753_vk_serialize(const mnt753_vk* vk, uint8_t* buf, size_t cap, size_t* l
 /* out_affine[i] = ABC_g1[0] + sum_j inputs[i][j] ABC_g1[j + 1] for i < n (inputs: n x num_inputs Fr, host memory; out: n G1 points,
  * affine wire form, the identity as zero words): the accumulation of r1cs_gg_ppzksnark_online_verifier_weak_IC (:522-525).  One lane
  * per proof, a joint double-and-add over the bits of its inputs: 753 doublings and on average 753 num_inputs / 2 additions in that
- * lane -- meant for the handful of public inputs of this project's systems, not for thousands.  MNT753_EINPUT: an input is >= r. */
+ * lane: right for a handful of public inputs.  A key with more of them is prepared once (mnt753_vk_prepare_inputs below) and this call,
+ * like the verifiers, then walks window tables -- the same words in out_affine.  MNT753_EINPUT: an input is >= r. */
 int mnt753_vk_accumulate(const mnt753_vk* vk, const uint64_t* inputs, size_t n, uint64_t* out_affine);
+/* ---- input tables of a key: public inputs by the fixed-base method ------------------------------------
+ * The ABC points of a key are fixed bases, so the accumulation of r1cs_gg_ppzksnark_online_verifier_weak_IC (r1cs_gg_ppzksnark.tcc:
+ * 522-525) can run as libff's get_window_table / windowed_exp / batch_exp (depends/libff/libff/algebra/scalar_multiplication/
+ * multiexp.tcc:547-720) with one table per ABC point: W = ceil(754 / w) mixed additions per input instead of 753 doublings and some
+ * 376 additions.  An opt-in property of the key OBJECT: nothing prepares a key by itself, no environment variable or process-wide
+ * setting is read, and a key that was not prepared launches exactly what it launched before.
+ * mnt753_vk_prepare_inputs builds one signed-digit window table (the layout of mnt753_fixed_base_create: multiples 1 .. 2^(w-1) of
+ * 2^(jw) ABC[p] for every window j, 256-byte affine rows) per ABC point, ABC[0] included, in ONE allocation owned by the key:
+ * (num_inputs + 1) W 2^(w-1) 256 bytes.  window_bits = 0: the widest w in 2 .. 16 whose tables fit max_table_bytes
+ * (0: 256 MiB, the Infinity Cache of the MI355X).  MNT753_EINVAL, with the key left as it was and a message that names the bytes
+ * needed and the cap: an explicit width that does not fit, w = 2 not fitting, window_bits outside 2 .. 16 (other than 0), a key
+ * without inputs.  Calling it again replaces the tables; mnt753_vk_release_inputs frees them and returns the key to the unprepared
+ * path; mnt753_vk_destroy frees them too.  mnt753_vk_coefficient_bytes keeps its meaning: the tables are reported by the plan only.
+ * The build is O(w) launches per 2^17 rows of a level, not a loop over the inputs.
+ * A prepared key takes the table path in mnt753_vk_accumulate, mnt753_groth16_verify, _verify_ex, _verify_compressed and
+ * _verify_folded: per chunk one lane per (proof, slice of inputs_per_lane consecutive inputs) walks its inputs' digits, one lane
+ * per proof sums ABC[0] and the proof's partial sums, and the accumulated points reach the pairing kernel word for word as
+ * k_vk_accumulate writes them -- verdicts, status bytes and the identity / input >= r cases are unchanged.  inputs_per_lane is chosen
+ * per chunk: as many slices as bring the chunk to 65536 lanes, one input per lane for a single proof, one lane per proof from 65536
+ * proofs on.  Workspace per proof of a chunk, beside what mnt753_vk_set_workspace_cap's comment lists: 336 (slices + 1) + 112
+ * bytes, slices = ceil(num_inputs / inputs_per_lane); the chunk is cap / (194 + 96 num_inputs + 336 (slices + 1) + 112) proofs, with
+ * inputs_per_lane chosen for the chunk that runs (a cap that shrinks the chunk gives its proofs more slices, settled in a few rounds).
+ * The fold with a prepared key: c_j for all inputs of a chunk from one launch over the columns (no gather, no host round trip per
+ * input), and S = rho ABC[0] + sum_j c_j ABC[j + 1] on the device as ONE walk over num_inputs + 1 scalars, ABC[0]'s table in place
+ * of the implicit 1.
+ * mnt753_vk_input_plan fills *out for a chunk of n proofs (n = 0 counts as 1): prepared = 0 and zeros for a key without tables. */
+typedef struct { int window_bits, windows; uint32_t inputs_per_lane; uint32_t reserved; uint64_t table_bytes; int prepared; int reserved2; } mnt753_vk_input_plan_t;
+int mnt753_vk_prepare_inputs(mnt753_vk* vk, int window_bits /* 0 = default */, size_t max_table_bytes /* 0 = 256 MiB */);
+int mnt753_vk_input_plan(const mnt753_vk* vk, size_t n /* proofs of a chunk, for inputs_per_lane */, mnt753_vk_input_plan_t* out);
+int mnt753_vk_release_inputs(mnt753_vk* vk);
 /* Verifies n proofs against the key: r1cs_gg_ppzksnark_online_verifier_weak_IC (:515-567) per proof, one lane group each.
  * proofs: n x (A | B | C), affine wire form, the layout `complete` writes; inputs: n x num_inputs Fr (without the leading 1);
  * on_device != 0: both are device pointers.  verdicts (host memory, n bytes): 0 accepted, 1 malformed, 2 the pairing check failed.

@@ -88,6 +88,13 @@ int mnt753_test_fold_parts(const mnt753_vk* vk, const uint64_t* proofs, const ui
 /* milliseconds on the device (HIP events) of the stages of the calling thread's last mnt753_groth16_verify_folded / mnt753_test_fold_parts:
  * [0] the scaling and the point sum, [1] the Miller loops and the products, [2] the tail (0 where it was skipped).  tools/bench_fold.py. */
 int mnt753_test_fold_last_timing(float out_ms[3]);
+/* The input tables of a key (mnt753_vk_prepare_inputs).  _force_inputs_per_lane: every later call on the key
+ * walks inputs_per_lane consecutive scalars per lane instead of the host's choice for the chunk (0: the host's choice again), so that a
+ * test reaches the partial sums of several slices -- a ragged last slice, a single slice -- at a small number of proofs; values above
+ * the number of scalars count as that number.  _last_timing: milliseconds on the device (HIP events) of [0] the walk and [1] the
+ * segment sum with the normalisation of the key's last chunk, and [2] of the last build of the tables.  tools/bench_vk_inputs.py. */
+int mnt753_test_vk_force_inputs_per_lane(mnt753_vk* vk, uint32_t inputs_per_lane);
+int mnt753_test_vk_inputs_last_timing(const mnt753_vk* vk, float out_ms[3]);
 
 /* The square root of csrc/fp_sqrt.hip.h on n raw field elements in wire form (host pointers): deg = 1 the base field Fq of the curve,
  * deg = 2 (MNT4753) / 3 (MNT6753) the coordinate field of G2, c0 | c1 [| c2].  The lane mapping is the product's (k_decompress): one

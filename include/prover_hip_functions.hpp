@@ -223,6 +223,23 @@ public:
   static decompressed_points decompress_points(int group, const uint64_t *x, const uint8_t *flags, size_t n);
   static std::vector<uint8_t> verify_compressed(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *x, const uint8_t *flags, const uint64_t *inputs,
                                                 size_t n, bool check_subgroup);
+  // Input tables (mnt753_vk_prepare_inputs), opt-in: with tables.enabled the key these calls make is prepared
+  // before it verifies -- one window table per ABC point, W = ceil(754 / w) additions per public input instead of a double-and-add over
+  // 753 bits; the same verdicts.  window_bits 0: the widest width whose tables fit max_table_bytes (0: 256 MiB); a width or a cap that
+  // cannot be met throws.  plan, where given, receives what was built.
+  struct input_table_plan { int window_bits, windows; uint64_t table_bytes; };
+  struct input_tables {
+    bool enabled = false;
+    int window_bits = 0;
+    size_t max_table_bytes = 0;
+    input_table_plan *plan = nullptr;
+  };
+  static std::vector<uint8_t> verify(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *proofs, const uint64_t *inputs, size_t n,
+                                     bool check_subgroup, const input_tables &tables);
+  static folded_verdict verify_folded(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *proofs, const uint64_t *inputs, size_t n,
+                                      const uint64_t *coefficients, const input_tables &tables);
+  static std::vector<uint8_t> verify_compressed(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *x, const uint8_t *flags, const uint64_t *inputs,
+                                                size_t n, bool check_subgroup, const input_tables &tables);
   // raw access for tests / tools
   static const uint64_t *G1_words(const G1 *a);
   static const uint64_t *G2_words(const G2 *a);

@@ -33,6 +33,12 @@ class CheckReport(C.Structure):
     _fields_ = [("n_bad", C.c_uint64), ("first_bad", C.c_uint64), ("first_reason", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class VkInputPlan(C.Structure):
+    """mnt753_vk_input_plan_t"""
+    _fields_ = [("window_bits", C.c_int), ("windows", C.c_int), ("inputs_per_lane", C.c_uint32), ("reserved", C.c_uint32),
+                ("table_bytes", C.c_uint64), ("prepared", C.c_int), ("reserved2", C.c_int)]
+
+
 class KeygenSizes(C.Structure):
     """mnt753_keygen_sizes"""
     _fields_ = [(k, C.c_uint64) for k in ("a_query", "b_g1_query", "b_g2_query", "l_query", "h_query", "abc_g1")]
@@ -191,6 +197,9 @@ def lib():
         "mnt753_vk_gt": (i, [vp, u64p]),
         "mnt753_vk_serialize": (i, [vp, vp, sz, C.POINTER(C.c_size_t)]),
         "mnt753_vk_accumulate": (i, [vp, u64p, sz, u64p]),
+        "mnt753_vk_prepare_inputs": (i, [vp, i, sz]),
+        "mnt753_vk_input_plan": (i, [vp, sz, C.POINTER(VkInputPlan)]),
+        "mnt753_vk_release_inputs": (i, [vp]),
         "mnt753_groth16_verify": (i, [vp, vp, vp, sz, i, vp, vp]),
         "mnt753_groth16_verify_ex": (i, [vp, vp, vp, sz, i, C.c_uint, vp, vp]),
         "mnt753_groth16_verify_folded": (i, [vp, vp, vp, sz, i, u64p, vp, C.POINTER(C.c_int), vp]),
@@ -245,6 +254,8 @@ def test_lib():
         "mnt753_test_reduce_capped": (i, [i, i, C.c_void_p, C.c_void_p, sz, u64p, C.c_uint, u64p]),
         "mnt753_test_fold_parts": (i, [C.c_void_p, u64p, u64p, sz, u64p, u64p, u64p, u64p, u64p, C.c_void_p, C.POINTER(C.c_int)]),
         "mnt753_test_fold_last_timing": (i, [C.POINTER(C.c_float)]),
+        "mnt753_test_vk_force_inputs_per_lane": (i, [C.c_void_p, C.c_uint32]),
+        "mnt753_test_vk_inputs_last_timing": (i, [C.c_void_p, C.POINTER(C.c_float)]),
         "mnt753_test_field_sqrt": (i, [i, i, u64p, sz, u64p, C.c_void_p]),
         "mnt753_test_field_sqrt_window": (i, [i, i, i, u64p, sz, u64p, C.c_void_p, C.POINTER(C.c_float)]),
     }
@@ -1253,6 +1264,36 @@ class VerificationKey:
         out = np.zeros((n, 24), dtype=np.uint64)
         _check(lib().mnt753_vk_accumulate(self._h, px, n, out.ctypes.data_as(C.POINTER(C.c_uint64))), "mnt753_vk_accumulate")
         return out
+
+    def prepare_inputs(self, window_bits=0, max_table_bytes=0):
+        """mnt753_vk_prepare_inputs: one signed-digit window table per ABC point on the device; accumulate(),
+        verify(), verify_compressed() and verify_folded() then walk the tables -- the same results, W = ceil(754 / w) additions per
+        input.  window_bits 0: the widest width in 2 .. 16 whose tables fit max_table_bytes (0: 256 MiB).  Opt-in: nothing prepares a
+        key by itself.  A refusal (Mnt753Error) leaves the key as it was.  Returns input_plan()."""
+        _check(lib().mnt753_vk_prepare_inputs(self._h, int(window_bits), int(max_table_bytes)), "mnt753_vk_prepare_inputs")
+        return self.input_plan()
+
+    def input_plan(self, n=1):
+        """mnt753_vk_input_plan for a chunk of n proofs -> dict: prepared, window_bits, windows, inputs_per_lane, table_bytes"""
+        out = VkInputPlan()
+        _check(lib().mnt753_vk_input_plan(self._h, int(n), C.byref(out)), "mnt753_vk_input_plan")
+        return {"prepared": bool(out.prepared), "window_bits": int(out.window_bits), "windows": int(out.windows),
+                "inputs_per_lane": int(out.inputs_per_lane), "table_bytes": int(out.table_bytes)}
+
+    def release_inputs(self):
+        """mnt753_vk_release_inputs: frees the input tables; the key is back on the path of an unprepared key"""
+        _check(lib().mnt753_vk_release_inputs(self._h), "mnt753_vk_release_inputs")
+
+    def test_force_inputs_per_lane(self, inputs_per_lane):
+        """mnt753_test_vk_force_inputs_per_lane (test library): scalars per lane of the walk of every later call (0: the host's choice)"""
+        _check(test_lib().mnt753_test_vk_force_inputs_per_lane(self._h, int(inputs_per_lane)), "mnt753_test_vk_force_inputs_per_lane")
+
+    def test_inputs_last_timing(self):
+        """mnt753_test_vk_inputs_last_timing (test library): milliseconds of the walk, of the segment sum with the normalisation (last
+        chunk) and of the last build of the tables"""
+        out = (C.c_float * 3)()
+        _check(test_lib().mnt753_test_vk_inputs_last_timing(self._h, out), "mnt753_test_vk_inputs_last_timing")
+        return [float(v) for v in out]
 
     def check_subgroup(self):
         """beta_g2 and delta_g2 of the key through check_subgroup -> (n_bad, first_bad: 0 = beta_g2, 1 = delta_g2, reason).  The key's

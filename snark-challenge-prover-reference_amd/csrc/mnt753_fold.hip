@@ -7,6 +7,7 @@
 #include "fold_api.hpp"
 #include "fold_kernels.hip.h"
 #include "host_field.hpp"
+#include "vk_inputs_api.hpp"
 #include "vk_object.hpp"
 
 namespace mnt753 {
@@ -19,8 +20,10 @@ constexpr size_t FOLD_MAX = (size_t)1 << 24;        // logical lanes are 32-bit;
 struct FoldBuffers {
   void *proofs = nullptr, *inputs = nullptr, *coef = nullptr, *rhom = nullptr, *ints = nullptr, *u = nullptr, *c = nullptr, *flags = nullptr,
        *partials = nullptr, *small = nullptr;
+  // a prepared key: the carried sums c_j, the num_inputs + 1 scalars of S as integers, and the workspace of their walk
+  void *cacc = nullptr, *sints = nullptr, *wpart = nullptr, *wsums = nullptr, *wpre = nullptr;
   ~FoldBuffers() {
-    for (void* p : {proofs, inputs, coef, rhom, ints, u, c, flags, partials, small})
+    for (void* p : {proofs, inputs, coef, rhom, ints, u, c, flags, partials, small, cacc, sints, wpart, wsums, wpre})
       if (p) (void)hipFree(p);
   }
 };
@@ -87,6 +90,19 @@ int fold_t(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, 
   // small: 256 point sums of workgroups | T | F | S, T in wire form | F in wire form | the verdict
   const size_t off_t = 256 * PB, off_f = off_t + PB, off_st = off_f + TB, off_fw = off_st + 2 * 192, off_acc = off_fw + 8 * wt;
   if (int rc = fold_alloc(&buf.small, off_acc + 16)) return rc;
+  const bool prepared = vk_inputs_prepared(vk);
+  const uint32_t s_ipl = prepared ? vk_inputs_per_lane(vk, 1, (uint32_t)ni + 1u) : 0u;
+  VkInputWs ws;
+  if (prepared) {
+    if (int rc = fold_alloc(&buf.cacc, 4 * (size_t)FPS_WORDS * ni)) return rc;
+    if (int rc = fold_alloc(&buf.sints, 96 * (ni + 1))) return rc;
+    if (int rc = fold_alloc(&buf.wpart, vk_inputs_partials_bytes(1, (uint32_t)ni + 1u, s_ipl))) return rc;
+    if (int rc = fold_alloc(&buf.wsums, vk_inputs_sums_bytes(1))) return rc;
+    if (int rc = fold_alloc(&buf.wpre, vk_inputs_pre_bytes(1))) return rc;
+    ws.partials = reinterpret_cast<uint32_t*>(buf.wpart);
+    ws.sums = reinterpret_cast<uint32_t*>(buf.wsums);
+    ws.pre = reinterpret_cast<uint32_t*>(buf.wpre);
+  }
   char* small = reinterpret_cast<char*>(buf.small);
   uint32_t *pt_part = reinterpret_cast<uint32_t*>(small), *t_acc = reinterpret_cast<uint32_t*>(small + off_t), *f_acc = reinterpret_cast<uint32_t*>(small + off_f),
            *st_wire = reinterpret_cast<uint32_t*>(small + off_st), *f_wire = reinterpret_cast<uint32_t*>(small + off_fw),
@@ -160,7 +176,12 @@ int fold_t(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, 
     HIP_TRY(hipGetLastError());
     // c_j += sum_i rho_i x_ij: one reduction over Fr per public input (mnt753_vec_dot); the column of input j is the input vector
     // itself for one input, else gathered into the room k_inputs_to_integer no longer needs
-    for (size_t j = 0; j < ni; ++j) {
+    // A prepared key: all columns in one launch, the sums carried on the device from chunk to chunk.
+    if (prepared) {
+      if (int rc = vk_inputs_dots_enqueue(curve, reinterpret_cast<const uint32_t*>(buf.rhom), reinterpret_cast<const uint32_t*>(di), cnt, (uint32_t)ni,
+                                          reinterpret_cast<uint32_t*>(buf.cacc), first ? 1 : 0, st)) return rc;
+    }
+    for (size_t j = 0; j < ni && !prepared; ++j) {
       const uint64_t* col = di;
       if (ni > 1) {
         HIP_TRY(hipMemcpy2DAsync(buf.ints, 96, reinterpret_cast<const char*>(di) + 96 * j, 96 * ni, 96, cnt, hipMemcpyDeviceToDevice, st));
@@ -176,10 +197,19 @@ int fold_t(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, 
     ev.add(ms[0], 0, 1);
     ev.add(ms[1], 1, 2);
   }
-  // S = rho ABC[0] + sum_j c_j ABC[j + 1] on the host: num_inputs + 1 scalings of single points (mnt753_point_scale / _add)
+  // S = rho ABC[0] + sum_j c_j ABC[j + 1]: on the device through the tables of a prepared key, else on the host by num_inputs + 1
+  // scalings of single points (mnt753_point_scale / _add)
   Fr rho_fr = Fr::from_words(rho) * r2;
   uint64_t s_aff[24];
-  {
+  if (prepared) {
+    // on the device, as ONE proof of num_inputs + 1 scalars against the tables of ABC[0 ..]: rho itself is an integer below r
+    uint32_t* sints = reinterpret_cast<uint32_t*>(buf.sints);
+    HIP_TRY(hipMemcpyAsync(sints, rho, 96, hipMemcpyHostToDevice, st));
+    if (int rc = vk_inputs_fold_scalars_enqueue(curve, reinterpret_cast<const uint32_t*>(buf.cacc), (uint32_t)ni, sints + 24, st)) return rc;
+    if (int rc = vk_inputs_enqueue(vk, sints, 1, (uint32_t)ni + 1u, 0u, nullptr, s_ipl, ws, st_wire, st)) return rc;
+    if (parts && parts->s) HIP_TRY(hipMemcpyAsync(s_aff, st_wire, 192, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));               // rho and s_aff are the stack's
+  } else {
     std::vector<uint64_t> p(36), q(36), sum(36);
     for (size_t j = 0; j <= ni; ++j) {
       if (int rc = mnt753_point_from_affine(curve, MNT753_G1, vk->abc.data() + 24 * j, p.data())) return rc;
@@ -189,7 +219,7 @@ int fold_t(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, 
     }
     if (int rc = mnt753_point_to_affine(curve, MNT753_G1, sum.data(), s_aff)) return rc;
   }
-  HIP_TRY(hipMemcpyAsync(st_wire, s_aff, 192, hipMemcpyHostToDevice, st));
+  if (!prepared) HIP_TRY(hipMemcpyAsync(st_wire, s_aff, 192, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL((k_fold_point_affine<C1>), dim3(1), dim3(64), 0, st, (const uint32_t*)t_acc, st_wire + 48);
   *accepted = 0;
   if (!flagged) {

@@ -8,6 +8,7 @@
 #include "compress_api.hpp"
 #include "mnt753_generators.h"
 #include "pairing_kernels.hip.h"
+#include "vk_inputs_api.hpp"
 #include "vk_object.hpp"
 
 namespace mnt753 {
@@ -16,8 +17,9 @@ namespace {
 // device memory of one call
 struct PairingBuffers {
   void *g1 = nullptr, *g2 = nullptr, *out = nullptr, *stand = nullptr, *ints = nullptr;
+  void *part = nullptr, *sums = nullptr, *pre = nullptr;   // a prepared key's walk: the partials, the sums, the prefix products (VkInputWs)
   ~PairingBuffers() {
-    for (void* p : {g1, g2, out, stand, ints})
+    for (void* p : {g1, g2, out, stand, ints, part, sums, pre})
       if (p) (void)hipFree(p);
   }
 };
@@ -37,6 +39,17 @@ int alloc(void** p, size_t bytes) {
     *p = nullptr;
     return set_error(MNT753_ENOMEM, "pairing: device allocation failed");
   }
+  return 0;
+}
+
+// the workspace of a prepared key's walk for chunks of `chunk` proofs at ipl inputs per lane
+int alloc_input_ws(PairingBuffers& buf, const mnt753_vk* vk, size_t chunk, uint32_t ipl, VkInputWs* ws) {
+  if (int rc = alloc(&buf.part, vk_inputs_partials_bytes(chunk, (uint32_t)vk->num_inputs, ipl))) return rc;
+  if (int rc = alloc(&buf.sums, vk_inputs_sums_bytes(chunk))) return rc;
+  if (int rc = alloc(&buf.pre, vk_inputs_pre_bytes(chunk))) return rc;
+  ws->partials = reinterpret_cast<uint32_t*>(buf.part);
+  ws->sums = reinterpret_cast<uint32_t*>(buf.sums);
+  ws->pre = reinterpret_cast<uint32_t*>(buf.pre);
   return 0;
 }
 
@@ -169,6 +182,7 @@ int mnt753_vk_create(int curve, const uint64_t* alpha_g1, const uint64_t* beta_g
 int mnt753_vk_destroy(mnt753_vk* vk) {
   if (!vk) return 0;
   OnDevice guard(vk->device);
+  (void)mnt753_vk_release_inputs(vk);
   if (vk->dev_key) (void)hipFree(vk->dev_key);
   if (vk->dev_abc) (void)hipFree(vk->dev_abc);
   if (vk->dev_coeffs) (void)hipFree(vk->dev_coeffs);
@@ -219,21 +233,28 @@ int mnt753_vk_serialize(const mnt753_vk* vk, uint8_t* buf, size_t cap, size_t* l
 
 namespace {
 // inputs (device, n x num_inputs Fr) -> dev_acc (n G1 points, affine wire form), dev_bad[t] = 1 where an input is >= r.  ints: room for
-// the inputs as integers, 96 num_inputs n bytes (unused without inputs).  Enqueues only.
-int accumulate_on_device(const mnt753_vk* vk, const uint64_t* dev_inputs, size_t n, uint64_t* dev_acc, uint8_t* dev_bad, uint32_t* ints, hipStream_t st) {
+// the inputs as integers, 96 num_inputs n bytes (unused without inputs).  Enqueues only.  A prepared key (ws, ipl: its workspace and the
+// inputs per lane of this call's chunks) walks its input tables instead of k_vk_accumulate: the same words in dev_acc.
+int accumulate_on_device(const mnt753_vk* vk, const uint64_t* dev_inputs, size_t n, uint64_t* dev_acc, uint8_t* dev_bad, uint32_t* ints, const VkInputWs* ws,
+                         uint32_t ipl, hipStream_t st) {
   const size_t ni = vk->num_inputs;
   if (!ni) HIP_TRY(hipMemsetAsync(dev_bad, 0, n, st));
   const dim3 g((unsigned)((n + 255) / 256)), b(256);
   const uint32_t* in = reinterpret_cast<const uint32_t*>(dev_inputs);
   const uint32_t* abc = reinterpret_cast<const uint32_t*>(vk->dev_abc);
   uint32_t* out = reinterpret_cast<uint32_t*>(dev_acc);
-  if (vk->curve == MNT753_CURVE_MNT4753) {
-    if (ni) hipLaunchKernelGGL((k_inputs_to_integer<MOD_A>), g, b, 0, st, in, ints, dev_bad, (uint32_t)n, (uint32_t)ni);
-    hipLaunchKernelGGL((k_vk_accumulate<Mnt4G1>), g, b, 0, st, abc, ints, out, (uint32_t)n, (uint32_t)ni);
-  } else {
-    if (ni) hipLaunchKernelGGL((k_inputs_to_integer<MOD_B>), g, b, 0, st, in, ints, dev_bad, (uint32_t)n, (uint32_t)ni);
-    hipLaunchKernelGGL((k_vk_accumulate<Mnt6G1>), g, b, 0, st, abc, ints, out, (uint32_t)n, (uint32_t)ni);
+  const bool mnt4 = vk->curve == MNT753_CURVE_MNT4753;
+  if (ni) {
+    if (mnt4) hipLaunchKernelGGL((k_inputs_to_integer<MOD_A>), g, b, 0, st, in, ints, dev_bad, (uint32_t)n, (uint32_t)ni);
+    else hipLaunchKernelGGL((k_inputs_to_integer<MOD_B>), g, b, 0, st, in, ints, dev_bad, (uint32_t)n, (uint32_t)ni);
   }
+  // the one difference between the two paths: the tables of a prepared key (which has inputs), or one lane per proof
+  if (vk_inputs_prepared(vk)) {
+    HIP_TRY(hipGetLastError());
+    return vk_inputs_enqueue(vk, ints, n, (uint32_t)ni, 1u, abc, ipl, *ws, out, st);
+  }
+  if (mnt4) hipLaunchKernelGGL((k_vk_accumulate<Mnt4G1>), g, b, 0, st, abc, ints, out, (uint32_t)n, (uint32_t)ni);
+  else hipLaunchKernelGGL((k_vk_accumulate<Mnt6G1>), g, b, 0, st, abc, ints, out, (uint32_t)n, (uint32_t)ni);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -259,8 +280,14 @@ int mnt753_vk_accumulate(const mnt753_vk* vk, const uint64_t* inputs, size_t n, 
   }
   if (int rc = alloc(&buf.out, 192 * n)) return rc;
   if (int rc = alloc(&buf.g2, n)) return rc;
+  VkInputWs ws;
+  uint32_t ipl = 0;
+  if (vk_inputs_prepared(vk)) {
+    ipl = vk_inputs_per_lane(vk, n, (uint32_t)ni);
+    if (int rc = alloc_input_ws(buf, vk, n, ipl, &ws)) return rc;
+  }
   if (int rc = accumulate_on_device(vk, reinterpret_cast<const uint64_t*>(buf.g1), n, reinterpret_cast<uint64_t*>(buf.out),
-                                    reinterpret_cast<uint8_t*>(buf.g2), reinterpret_cast<uint32_t*>(buf.ints), nullptr)) return rc;
+                                    reinterpret_cast<uint8_t*>(buf.g2), reinterpret_cast<uint32_t*>(buf.ints), &ws, ipl, nullptr)) return rc;
   HIP_TRY(hipStreamSynchronize(nullptr));
   std::vector<uint8_t> bad(n);
   HIP_TRY(hipMemcpy(bad.data(), buf.g2, n, hipMemcpyDeviceToHost));
@@ -298,9 +325,28 @@ int verify_chunks(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* c
   // what one proof of a chunk takes: the accumulated point, the inputs as integers, flag and verdict, and its staged copy if it
   // arrives in host memory; a compressed proof: its decompressed words as well.  The cap of the key bounds the chunk (at least one
   // proof, at most 2^16).
-  const size_t per_proof = 194 + 96 * ni + (compressed ? 8 * pw : 0) + (on_device ? 0 : (compressed ? 8 * xw + 3 : 8 * pw) + 96 * ni);
+  // A prepared key: the partials, the sum and the prefix product of its walk as well, at the inputs per lane of the uncapped chunk.
+  // The inputs per lane belong to the chunk that runs: a cap that shrinks the chunk asks for more slices per proof, whose partials
+  // shrink it again -- settled in a few rounds (the chunk only falls, the slices only rise; the last round's pair is kept).
   size_t chunk = n < VERIFY_CHUNK ? n : VERIFY_CHUNK;
-  if (vk->workspace_cap && vk->workspace_cap / per_proof < chunk) chunk = vk->workspace_cap / per_proof ? vk->workspace_cap / per_proof : 1;
+  const bool prepared = vk_inputs_prepared(vk);
+  const size_t base_per_proof = 194 + 96 * ni + (compressed ? 8 * pw : 0) + (on_device ? 0 : (compressed ? 8 * xw + 3 : 8 * pw) + 96 * ni);
+  uint32_t ipl = prepared ? vk_inputs_per_lane(vk, chunk, (uint32_t)ni) : 0u;
+  for (int round = 0; round < 8; ++round) {
+    const size_t per_proof = base_per_proof + (prepared ? (size_t)vki_workspace_per_proof((uint32_t)ni, ipl) : 0);
+    size_t fits = chunk;
+    if (vk->workspace_cap && vk->workspace_cap / per_proof < chunk) fits = vk->workspace_cap / per_proof ? vk->workspace_cap / per_proof : 1;
+    const uint32_t next = prepared ? vk_inputs_per_lane(vk, fits, (uint32_t)ni) : 0u;
+    const bool settled = fits == chunk && next == ipl;
+    chunk = fits;
+    if (settled || !prepared) break;
+    if (next < ipl) ipl = next;          // more slices for the smaller chunk; never fewer, so that the rounds end
+    else break;
+  }
+  if (prepared && vk->workspace_cap) {   // (rounds that did not settle: the chunk of the last pair still has to fit its own slices)
+    const size_t per_proof = base_per_proof + (size_t)vki_workspace_per_proof((uint32_t)ni, ipl);
+    if (vk->workspace_cap / per_proof < chunk) chunk = vk->workspace_cap / per_proof ? vk->workspace_cap / per_proof : 1;
+  }
   PairingBuffers buf;   // g1: staged (or decompressed) proofs, g2: staged inputs, out: accumulated points, stand: flags then verdicts, ints: inputs as integers
   CompressedStage cs;   // the staged compressed proofs of a host batch, and the record of the decompression (not read: the verdicts tell)
   if (!on_device || compressed) {
@@ -320,6 +366,8 @@ int verify_chunks(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* c
   if (ni) { if (int rc = alloc(&buf.ints, 96 * ni * chunk)) return rc; }
   if (int rc = alloc(&buf.out, 192 * chunk)) return rc;
   if (int rc = alloc(&buf.stand, 2 * chunk)) return rc;
+  VkInputWs ws;
+  if (prepared) { if (int rc = alloc_input_ws(buf, vk, chunk, ipl, &ws)) return rc; }
   uint8_t* dev_bad = reinterpret_cast<uint8_t*>(buf.stand);
   uint8_t* dev_verdicts = dev_bad + chunk;
   size_t rejected = 0;
@@ -354,7 +402,7 @@ int verify_chunks(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* c
         di = reinterpret_cast<const uint64_t*>(buf.g2);
       }
     }
-    if (int rc = accumulate_on_device(vk, di, cnt, reinterpret_cast<uint64_t*>(buf.out), dev_bad, reinterpret_cast<uint32_t*>(buf.ints), st)) return rc;
+    if (int rc = accumulate_on_device(vk, di, cnt, reinterpret_cast<uint64_t*>(buf.out), dev_bad, reinterpret_cast<uint32_t*>(buf.ints), &ws, ipl, st)) return rc;
     const uint32_t *p = reinterpret_cast<const uint32_t*>(dp), *acc = reinterpret_cast<const uint32_t*>(buf.out),
                    *key = reinterpret_cast<const uint32_t*>(vk->dev_key);
     if (vk->curve == MNT753_CURVE_MNT4753) {

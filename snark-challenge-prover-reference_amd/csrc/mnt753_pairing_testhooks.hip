@@ -9,6 +9,7 @@
 #include "../../include/mnt753_hip_test.h"
 #include "fold_api.hpp"
 #include "pairing_kernels.hip.h"
+#include "vk_inputs_api.hpp"
 
 using namespace mnt753;
 
@@ -132,4 +133,13 @@ extern "C" int mnt753_test_fold_last_timing(float out_ms[3]) {
   if (!out_ms) return set_error(MNT753_EINVAL, "test_fold_last_timing: bad argument");
   groth16_fold_last_timing(out_ms);
   return 0;
+}
+extern "C" int mnt753_test_vk_force_inputs_per_lane(mnt753_vk* vk, uint32_t inputs_per_lane) {
+  if (!vk) return set_error(MNT753_EINVAL, "test_vk_force_inputs_per_lane: bad argument");
+  vk->test_inputs_per_lane = inputs_per_lane;
+  return 0;
+}
+extern "C" int mnt753_test_vk_inputs_last_timing(const mnt753_vk* vk, float out_ms[3]) {
+  if (!vk || !out_ms) return set_error(MNT753_EINVAL, "test_vk_inputs_last_timing: bad argument");
+  return vk_inputs_last_timing(vk, out_ms, out_ms + 1, out_ms + 2);
 }

@@ -616,7 +616,8 @@ __global__ void __launch_bounds__(256) k_inputs_to_integer(const uint32_t* __res
 // acc[t] = ABC[0] + sum_j input[t][j] ABC[j + 1], affine wire form (the identity: all words zero), one lane per proof: a joint
 // double-and-add over the 753 bits of all inputs -- per bit one doubling and one mixed addition for every input whose bit is set,
 // through one instance of the point VM -- then one inversion.  753 (1 + num_inputs / 2) group operations per proof on average in one
-// lane: right for the handful of public inputs of this project's systems, not for thousands (an MSM per proof would be).
+// lane: right for a handful of public inputs.  A key with tens to thousands of them is prepared (mnt753_vk_prepare_inputs) and then
+// runs k_vk_walk / k_vk_segment_sum over window tables instead (vk_input_kernels.hip.h), which write the same words.
 template <class C1>
 __global__ void __launch_bounds__(256, 1) k_vk_accumulate(const uint32_t* __restrict__ abc, const uint32_t* __restrict__ ints, uint32_t* __restrict__ out,
                                                          uint32_t n, uint32_t num_inputs) {

@@ -14,4 +14,14 @@ struct mnt753_vk {
   uint64_t* dev_abc = nullptr;   // num_inputs + 1 G1 points
   uint32_t* dev_coeffs = nullptr;   // the Miller-loop coefficients of G2::one(), then of delta_g2 (k_g2_precompute)
   size_t workspace_cap = 0;      // bytes a verify call may allocate; 0: the default chunk of 2^16 proofs
+  // the input tables (mnt753_vk_prepare_inputs, mnt753_vk_inputs.hip): one signed-digit window table per ABC
+  // point in one allocation, window j of point p being window p in_W + j of one long table of batch_exp's layout.  nullptr: the key
+  // was not prepared and every call launches k_vk_accumulate.
+  uint32_t* dev_in_table = nullptr;
+  int in_w = 0, in_W = 0;
+  size_t in_table_bytes = 0;
+  float in_build_ms = 0.f;
+  void* in_ev[3] = {nullptr, nullptr, nullptr};   // hipEvent_t: around the walk and the segment sum of the last chunk (the test library reads them)
+  mutable bool in_timed = false;
+  uint32_t test_inputs_per_lane = 0;   // the test library's hook: scalars per lane of the walk instead of the host's choice
 };

@@ -611,7 +611,29 @@ static bool fold_coefficients(const char* path, size_t n, std::vector<uint64_t>&
       if (getrandom(&out[2 * k], 16, 0) != 16) { fprintf(stderr, "main_hip: getrandom failed\n"); return false; }
   return true;
 }
-struct VerifyOptions { bool check_subgroup = false, fold = false, compressed = false; const char* fold_file = nullptr; };
+struct VerifyOptions {
+  bool check_subgroup = false, fold = false, compressed = false, input_tables = false, quiet = false;
+  int input_window_bits = 0;   // --input-window-bits: 0 leaves the width to the library
+  const char* fold_file = nullptr;
+};
+// --input-tables: the key of every B::verify* call below is prepared first (mnt753_vk_prepare_inputs); the
+// first call that builds tables prints their plan unless --quiet
+template <typename B>
+struct TablePlanLine {
+  typename B::input_table_plan plan{0, 0, 0};
+  typename B::input_tables tables;
+  bool printed = false;
+  explicit TablePlanLine(const VerifyOptions& vo) {
+    tables.enabled = vo.input_tables;
+    tables.window_bits = vo.input_window_bits;
+    tables.plan = &plan;
+  }
+  void print(const VerifyOptions& vo) {
+    if (!vo.input_tables || vo.quiet || printed) return;
+    printf("input tables: w = %d, W = %d, %llu bytes\n", plan.window_bits, plan.windows, (unsigned long long)plan.table_bytes);
+    printed = true;
+  }
+};
 
 // ---- compressed proofs: libff's stream of A | B | C with point compression on, 390 (MNT4753) or 486 (MNT6753) bytes ----
 // the records of a proof: group and words of x, in the order of the file
@@ -687,7 +709,9 @@ static int verify_compressed_batch(const VerifyOptions& vo, const std::vector<ui
       return 3;
     }
   }
-  const std::vector<uint8_t> verdicts = B::verify_compressed(el.data(), num_inputs, x.data(), flags.data(), per_proof.data(), n, vo.check_subgroup);
+  TablePlanLine<B> tp(vo);
+  const std::vector<uint8_t> verdicts = B::verify_compressed(el.data(), num_inputs, x.data(), flags.data(), per_proof.data(), n, vo.check_subgroup, tp.tables);
+  tp.print(vo);
   int bad = 0;
   for (size_t k = 0; k < n; ++k) {
     printf("%s\n", verdicts[k] == 0 ? "VERIFIED" : (verdicts[k] == 3 ? "REJECTED (B not in the subgroup)" : (verdicts[k] == 1 ? "REJECTED (malformed)" : "REJECTED")));
@@ -700,6 +724,7 @@ template <typename B>
 static int verify_batch(const VerifyOptions& vo, const std::vector<uint64_t>& el, size_t num_inputs, const std::vector<uint64_t>& proofs,
                         const std::vector<uint64_t>& per_proof, size_t n, const std::vector<uint64_t>& coef) {
   std::vector<uint8_t> verdicts;
+  TablePlanLine<B> tp(vo);
   if (vo.check_subgroup) {
     // beta_g2 | delta_g2 lie side by side in the file
     const auto e = B::check_subgroup(el.data() + 24, 2);
@@ -707,14 +732,19 @@ static int verify_batch(const VerifyOptions& vo, const std::vector<uint64_t>& el
       fprintf(stderr, "main_hip: %s of the key: %s\n", e.first_bad == 0 ? "beta_g2" : "delta_g2", B::check_reason_text(e.reason));
       return 3;
     }
-    if (vo.fold && B::verify_folded(el.data(), num_inputs, proofs.data(), per_proof.data(), n, coef.data()).accepted) {
-      printf("VERIFIED %zu proofs (folded)\n", n);
-      return 0;
+    if (vo.fold) {
+      const bool accepted = B::verify_folded(el.data(), num_inputs, proofs.data(), per_proof.data(), n, coef.data(), tp.tables).accepted;
+      tp.print(vo);
+      if (accepted) {
+        printf("VERIFIED %zu proofs (folded)\n", n);
+        return 0;
+      }
     }
-    verdicts = B::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n, true);
+    verdicts = B::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n, true, tp.tables);
   } else {
-    verdicts = B::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n);
+    verdicts = B::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n, false, tp.tables);
   }
+  tp.print(vo);
   int bad = 0;
   for (size_t k = 0; k < n; ++k) {
     printf("%s\n", verdicts[k] == 0 ? "VERIFIED" : (verdicts[k] == 3 ? "REJECTED (B not in the subgroup)" : "REJECTED"));
@@ -843,7 +873,7 @@ static const char check_usage[] =
     "usage: %s MNT4753|MNT6753 check <params> [<input>] [--subgroup] [--gpus N]\n       %s MNT4753|MNT6753 check-r1cs <params> <r1cs> <witness> [--gpus N]\n"
     "  --subgroup: the B2 points must also lie in G2, the order-r subgroup of the twist (\"not in the subgroup\")\n";
 static const char vk_usage[] =
-    "usage: %s MNT4753|MNT6753 vk <vk_elements.bin> <out>\n       %s MNT4753|MNT6753 verify <vk_elements.bin> <input_or_witness> <proof> [<proof> ...] [--check-subgroup] [--fold [--fold-coefficients <file>]]\n"
+    "usage: %s MNT4753|MNT6753 vk <vk_elements.bin> <out>\n       %s MNT4753|MNT6753 verify <vk_elements.bin> <input_or_witness> <proof> [<proof> ...] [--check-subgroup] [--fold [--fold-coefficients <file>]] [--compressed] [--input-tables [--input-window-bits w]] [--quiet]\n"
     "  vk: writes the complete verification key (with the GT element e(alpha_g1, beta_g2)) in the reference's vk.txt format.\n"
     "  verify: prints VERIFIED or REJECTED per proof; exit code 0 if every proof is accepted, 3 otherwise.\n"
     "  --check-subgroup: beta_g2 and delta_g2 of the key and B of every proof must lie in G2, the order-r subgroup of the twist;\n"
@@ -851,7 +881,10 @@ static const char vk_usage[] =
     "  --fold: the batch under one final exponentiation first (random coefficients, or n x 16 bytes from --fold-coefficients);\n"
     "    accepted: one line naming the count, exit 0; rejected: the per-proof lines of --check-subgroup, exit 3.\n"
     "  --compressed: the proof files are libff's compressed streams (compress-proof); a proof that does not decompress prints\n"
-    "    REJECTED (malformed).  Not with --fold.\n";
+    "    REJECTED (malformed).  Not with --fold.\n"
+    "  --input-tables: the key is prepared before it verifies -- one window table per ABC point, W = ceil(754 / w) additions per public\n"
+    "    input; the same lines and exit codes.  Prints one line \"input tables: w = .., W = .., .. bytes\" first unless --quiet.\n"
+    "    --input-window-bits w: the width, 2 .. 16 (default: the widest whose tables fit 256 MiB).  Worth it from tens of inputs on.\n";
 static const char proof_stream_usage[] =
     "usage: %s MNT4753|MNT6753 compress-proof <proof> <out>\n       %s MNT4753|MNT6753 decompress-proof <in> <out>\n"
     "  compress-proof: A | B | C in wire words -> libff's stream with point compression on (390 / 486 bytes); validates nothing.\n"
@@ -1009,7 +1042,8 @@ static int vk_command(const Command& self, Options&, int argc, char** argv) {
   const int curve = parse_curve(argv[1]);
   if (curve < 0) return unknown_curve(argv[1]);
   std::vector<Flag> flags;
-  if (verify) flags = {{"--check-subgroup", false}, {"--fold", false}, {"--fold-coefficients", true}, {"--compressed", false}};
+  if (verify) flags = {{"--check-subgroup", false}, {"--fold", false}, {"--fold-coefficients", true}, {"--compressed", false},
+                       {"--input-tables", false}, {"--input-window-bits", true}, {"--quiet", false}};
   ArgScan a{argc, argv, 3, flags};
   std::vector<const char*> pos;
   VerifyOptions vo;
@@ -1018,11 +1052,20 @@ static int vk_command(const Command& self, Options&, int argc, char** argv) {
     else if (a.is("--compressed")) vo.compressed = true;
     else if (a.is("--fold")) vo.fold = vo.check_subgroup = true;
     else if (a.is("--fold-coefficients")) vo.fold_file = a.value;
+    else if (a.is("--input-tables")) vo.input_tables = true;
+    else if (a.is("--quiet")) vo.quiet = true;
+    else if (a.is("--input-window-bits")) {
+      char* end = nullptr;
+      const long w = strtol(a.value, &end, 10);
+      if (!*a.value || *end || w < 2 || w > 16) { fprintf(stderr, "main_hip: --input-window-bits %s: not a width in 2 .. 16\n", a.value); return 2; }
+      vo.input_window_bits = (int)w;
+    }
     else pos.push_back(a.value);
   }
   if (a.refused) return 2;
   if (verify ? pos.size() < 3 : pos.size() != 2) return usage(self.usage, argv[0]);
   if (vo.compressed && vo.fold) { fprintf(stderr, "main_hip: --fold takes no compressed proofs\n"); return 2; }
+  if (vo.input_window_bits && !vo.input_tables) { fprintf(stderr, "main_hip: --input-window-bits goes with --input-tables\n"); return 2; }
   return vk_or_verify(curve, verify, pos, vo);
 }
 

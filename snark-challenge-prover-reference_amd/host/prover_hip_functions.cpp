@@ -1477,28 +1477,60 @@ template <int CURVE> std::vector<uint8_t> HIP_B::verify(const uint64_t* vk_eleme
 }
 template <int CURVE> std::vector<uint8_t> HIP_B::verify(const uint64_t* vk_elements, size_t num_inputs, const uint64_t* proofs, const uint64_t* inputs, size_t n,
                                                         bool check_subgroup) {
-  const size_t w2 = mnt753_affine_words(CURVE, MNT753_G2);
+  return verify(vk_elements, num_inputs, proofs, inputs, n, check_subgroup, input_tables{});
+}
+// the key of one call: created, prepared where the caller asked for input tables, destroyed with the call
+namespace {
+struct CallKey {
   mnt753_vk* vk = nullptr;
-  check(mnt753_vk_create(CURVE, vk_elements, vk_elements + 24, vk_elements + 24 + w2, vk_elements + 24 + 2 * w2, num_inputs, &vk), "mnt753_vk_create");
+  ~CallKey() { mnt753_vk_destroy(vk); }
+};
+}  // namespace
+template <int CURVE, class Tables> static void make_call_key(CallKey& key, const uint64_t* vk_elements, size_t num_inputs, const Tables& tables) {
+  const size_t w2 = mnt753_affine_words(CURVE, MNT753_G2);
+  check(mnt753_vk_create(CURVE, vk_elements, vk_elements + 24, vk_elements + 24 + w2, vk_elements + 24 + 2 * w2, num_inputs, &key.vk), "mnt753_vk_create");
+  if (!tables.enabled) return;
+  check(mnt753_vk_prepare_inputs(key.vk, tables.window_bits, tables.max_table_bytes), "mnt753_vk_prepare_inputs");
+  if (tables.plan) {
+    mnt753_vk_input_plan_t p;
+    check(mnt753_vk_input_plan(key.vk, 1, &p), "mnt753_vk_input_plan");
+    tables.plan->window_bits = p.window_bits;
+    tables.plan->windows = p.windows;
+    tables.plan->table_bytes = p.table_bytes;
+  }
+}
+template <int CURVE> std::vector<uint8_t> HIP_B::verify(const uint64_t* vk_elements, size_t num_inputs, const uint64_t* proofs, const uint64_t* inputs, size_t n,
+                                                        bool check_subgroup, const input_tables& tables) {
+  CallKey key;
+  make_call_key<CURVE>(key, vk_elements, num_inputs, tables);
   std::vector<uint8_t> verdicts(n);
-  const int rc = check_subgroup ? mnt753_groth16_verify_ex(vk, proofs, inputs, n, 0, MNT753_VERIFY_CHECK_SUBGROUP, verdicts.data(), nullptr)
-                                : mnt753_groth16_verify(vk, proofs, inputs, n, 0, verdicts.data(), nullptr);
-  mnt753_vk_destroy(vk);
+  const int rc = check_subgroup ? mnt753_groth16_verify_ex(key.vk, proofs, inputs, n, 0, MNT753_VERIFY_CHECK_SUBGROUP, verdicts.data(), nullptr)
+                                : mnt753_groth16_verify(key.vk, proofs, inputs, n, 0, verdicts.data(), nullptr);
   if (rc < 0) check(rc, "mnt753_groth16_verify");
   return verdicts;
 }
 template <int CURVE> typename HIP_B::folded_verdict HIP_B::verify_folded(const uint64_t* vk_elements, size_t num_inputs, const uint64_t* proofs, const uint64_t* inputs,
-                                                                        size_t n, const uint64_t* coefficients) {
-  const size_t w2 = mnt753_affine_words(CURVE, MNT753_G2);
-  mnt753_vk* vk = nullptr;
-  check(mnt753_vk_create(CURVE, vk_elements, vk_elements + 24, vk_elements + 24 + w2, vk_elements + 24 + 2 * w2, num_inputs, &vk), "mnt753_vk_create");
+                                                                        size_t n, const uint64_t* coefficients, const input_tables& tables) {
+  CallKey key;
+  make_call_key<CURVE>(key, vk_elements, num_inputs, tables);
   folded_verdict out{false, std::vector<uint8_t>(n)};
   int accepted = 0;
-  const int rc = mnt753_groth16_verify_folded(vk, proofs, inputs, n, 0, coefficients, out.status.data(), &accepted, nullptr);
-  mnt753_vk_destroy(vk);
-  check(rc, "mnt753_groth16_verify_folded");
+  check(mnt753_groth16_verify_folded(key.vk, proofs, inputs, n, 0, coefficients, out.status.data(), &accepted, nullptr), "mnt753_groth16_verify_folded");
   out.accepted = accepted != 0;
   return out;
+}
+template <int CURVE> std::vector<uint8_t> HIP_B::verify_compressed(const uint64_t* vk_elements, size_t num_inputs, const uint64_t* x, const uint8_t* flags,
+                                                                   const uint64_t* inputs, size_t n, bool check_subgroup, const input_tables& tables) {
+  CallKey key;
+  make_call_key<CURVE>(key, vk_elements, num_inputs, tables);
+  std::vector<uint8_t> verdicts(n);
+  const int rc = mnt753_groth16_verify_compressed(key.vk, x, flags, inputs, n, 0, check_subgroup ? MNT753_VERIFY_CHECK_SUBGROUP : 0u, verdicts.data(), nullptr);
+  if (rc < 0) check(rc, "mnt753_groth16_verify_compressed");
+  return verdicts;
+}
+template <int CURVE> typename HIP_B::folded_verdict HIP_B::verify_folded(const uint64_t* vk_elements, size_t num_inputs, const uint64_t* proofs, const uint64_t* inputs,
+                                                                        size_t n, const uint64_t* coefficients) {
+  return verify_folded(vk_elements, num_inputs, proofs, inputs, n, coefficients, input_tables{});
 }
 template <int CURVE> typename HIP_B::compressed_points HIP_B::compress_points(int group, const uint64_t* affine, size_t n) {
   compressed_points out{std::vector<uint64_t>(n * mnt753_compressed_words(CURVE, group)), std::vector<uint8_t>(n)};
@@ -1514,14 +1546,7 @@ template <int CURVE> typename HIP_B::decompressed_points HIP_B::decompress_point
 }
 template <int CURVE> std::vector<uint8_t> HIP_B::verify_compressed(const uint64_t* vk_elements, size_t num_inputs, const uint64_t* x, const uint8_t* flags,
                                                                    const uint64_t* inputs, size_t n, bool check_subgroup) {
-  const size_t w2 = mnt753_affine_words(CURVE, MNT753_G2);
-  mnt753_vk* vk = nullptr;
-  check(mnt753_vk_create(CURVE, vk_elements, vk_elements + 24, vk_elements + 24 + w2, vk_elements + 24 + 2 * w2, num_inputs, &vk), "mnt753_vk_create");
-  std::vector<uint8_t> verdicts(n);
-  const int rc = mnt753_groth16_verify_compressed(vk, x, flags, inputs, n, 0, check_subgroup ? MNT753_VERIFY_CHECK_SUBGROUP : 0u, verdicts.data(), nullptr);
-  mnt753_vk_destroy(vk);
-  if (rc < 0) check(rc, "mnt753_groth16_verify_compressed");
-  return verdicts;
+  return verify_compressed(vk_elements, num_inputs, x, flags, inputs, n, check_subgroup, input_tables{});
 }
 
 template class mnt753_hip_impl<0>;

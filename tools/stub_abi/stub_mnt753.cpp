@@ -311,6 +311,17 @@ int mnt753_vk_accumulate(const mnt753_vk* vk, const uint64_t* inputs, size_t n, 
   for (size_t i = 0; i < 24 * n; ++i) out[i] = i;
   return 0;
 }
+// input tables: no table, the plan of the widths asked for (default: 4); the refusals of the product
+int mnt753_vk_prepare_inputs(mnt753_vk* vk, int window_bits, size_t) {
+  if (!vk || !vk->num_inputs || (window_bits && (window_bits < 2 || window_bits > 16))) return fail(MNT753_EINVAL, "vk_prepare_inputs: bad argument");
+  return 0;
+}
+int mnt753_vk_input_plan(const mnt753_vk* vk, size_t, mnt753_vk_input_plan_t* out) {
+  if (!vk || !out) return fail(MNT753_EINVAL, "vk_input_plan: bad argument");
+  *out = mnt753_vk_input_plan_t{4, 189, 1u, 0u, (uint64_t)(vk->num_inputs + 1) * 189 * 8 * 256, 1, 0};
+  return 0;
+}
+int mnt753_vk_release_inputs(mnt753_vk* vk) { return vk ? 0 : fail(MNT753_EINVAL, "vk_release_inputs: bad argument"); }
 // with MNT753_VERIFY_CHECK_SUBGROUP, MNT753_STUB_BAD_B=<index> gives that proof verdict 3
 int mnt753_groth16_verify_ex(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int, unsigned flags, uint8_t* verdicts, void*) {
   if (!vk || (n && (!proofs || !verdicts)) || (flags & ~MNT753_VERIFY_CHECK_SUBGROUP)) return fail(MNT753_EINVAL, "groth16_verify: bad argument");
