@@ -95,6 +95,11 @@ int mnt753_test_fold_last_timing(float out_ms[3]);
  * segment sum with the normalisation of the key's last chunk, and [2] of the last build of the tables.  tools/bench_vk_inputs.py. */
 int mnt753_test_vk_force_inputs_per_lane(mnt753_vk* vk, uint32_t inputs_per_lane);
 int mnt753_test_vk_inputs_last_timing(const mnt753_vk* vk, float out_ms[3]);
+/* Overwrites the key's e(alpha_g1, beta_g2) with gt_words (mnt753_gt_words words, host pointer; any words, canonical or not): the copy
+ * on the device that every verification compares against and the host copy mnt753_vk_gt / _serialize read.  Nothing else of the key
+ * changes.  For the near-miss tests of the accept / reject comparison (tests/test_pairing_designed_gpu.py): a key whose GT element
+ * differs from the true one in one bit must reject the proof the true key accepts, whichever bit it is. */
+int mnt753_test_vk_set_gt(mnt753_vk* vk, const uint64_t* gt_words);
 
 /* The square root of csrc/fp_sqrt.hip.h on n raw field elements in wire form (host pointers): deg = 1 the base field Fq of the curve,
  * deg = 2 (MNT4753) / 3 (MNT6753) the coordinate field of G2, c0 | c1 [| c2].  The lane mapping is the product's (k_decompress): one

@@ -256,6 +256,7 @@ def test_lib():
         "mnt753_test_fold_last_timing": (i, [C.POINTER(C.c_float)]),
         "mnt753_test_vk_force_inputs_per_lane": (i, [C.c_void_p, C.c_uint32]),
         "mnt753_test_vk_inputs_last_timing": (i, [C.c_void_p, C.POINTER(C.c_float)]),
+        "mnt753_test_vk_set_gt": (i, [C.c_void_p, u64p]),
         "mnt753_test_field_sqrt": (i, [i, i, u64p, sz, u64p, C.c_void_p]),
         "mnt753_test_field_sqrt_window": (i, [i, i, i, u64p, sz, u64p, C.c_void_p, C.POINTER(C.c_float)]),
     }
@@ -1294,6 +1295,13 @@ class VerificationKey:
         out = (C.c_float * 3)()
         _check(test_lib().mnt753_test_vk_inputs_last_timing(self._h, out), "mnt753_test_vk_inputs_last_timing")
         return [float(v) for v in out]
+
+    def test_set_gt(self, words):
+        """mnt753_test_vk_set_gt (test library): overwrites the key's e(alpha_g1, beta_g2), on the device and on the host"""
+        g, pg = _u64(np.asarray(words).reshape(-1))
+        if g.size != gt_words(self.curve):
+            raise Mnt753Error("test_set_gt: gt_words(curve) words")
+        _check(test_lib().mnt753_test_vk_set_gt(self._h, pg), "mnt753_test_vk_set_gt")
 
     def check_subgroup(self):
         """beta_g2 and delta_g2 of the key through check_subgroup -> (n_bad, first_bad: 0 = beta_g2, 1 = delta_g2, reason).  The key's

@@ -412,9 +412,19 @@ __global__ void __launch_bounds__(256, 1) k_fold_tail(const uint32_t* __restrict
   tower_load<F>(r, facc);
   T::mul(f, f, r);
   A::final_exponentiation(r, f);
+  // wire_load keeps 756 bits of a component and reduces what it keeps: a stored e(alpha, beta) that is not canonical would be compared
+  // as another element's words, so it accepts nothing (k_groth16_verify compares the words themselves)
+  bool nc = false;
+  if constexpr (F::LANES == 1) {
+    for (int k = 0; k < 2 * F::DEG; ++k) nc |= wire_noncanonical<F::MOD>(gt + 24 * k);
+  } else {
+    const int comp = (int)lane_comp<F>();
+    nc = wire_noncanonical<F::MOD>(gt + 24 * comp) || wire_noncanonical<F::MOD>(gt + W2 + 24 * comp);
+  }
+  const bool canonical = group_all<F>(!nc);
   wire_load<F>(f.c0, gt); wire_load<F>(f.c1, gt + W2);
   T::pow(want, f, rho.w, bits);
-  const bool same = A::f_equal(r.c0, want.c0) && A::f_equal(r.c1, want.c1);
+  const bool same = A::f_equal(r.c0, want.c0) && A::f_equal(r.c1, want.c1) && canonical;
   if (lane_comp<F>() == 0) *accepted = same ? 1u : 0u;
 }
 #endif  // __HIPCC__

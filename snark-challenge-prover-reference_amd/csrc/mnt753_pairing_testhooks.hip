@@ -139,6 +139,16 @@ extern "C" int mnt753_test_vk_force_inputs_per_lane(mnt753_vk* vk, uint32_t inpu
   vk->test_inputs_per_lane = inputs_per_lane;
   return 0;
 }
+extern "C" int mnt753_test_vk_set_gt(mnt753_vk* vk, const uint64_t* gt_words) {
+  if (!vk || !gt_words || !vk->dev_key) return set_error(MNT753_EINVAL, "test_vk_set_gt: bad argument");
+  if (int rc = require_device()) return rc;
+  OnDevice guard(vk->device);
+  const size_t w2 = mnt753_affine_words(vk->curve, MNT753_G2), wt = mnt753_gt_words(vk->curve);
+  HIP_TRY(hipDeviceSynchronize());                   // no call on the key is reading the old words
+  HIP_TRY(hipMemcpy(vk->dev_key + 24 + 2 * w2, gt_words, 8 * wt, hipMemcpyHostToDevice));
+  vk->gt.assign(gt_words, gt_words + wt);
+  return 0;
+}
 extern "C" int mnt753_test_vk_inputs_last_timing(const mnt753_vk* vk, float out_ms[3]) {
   if (!vk || !out_ms) return set_error(MNT753_EINVAL, "test_vk_inputs_last_timing: bad argument");
   return vk_inputs_last_timing(vk, out_ms, out_ms + 1, out_ms + 2);

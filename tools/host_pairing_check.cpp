@@ -101,7 +101,85 @@ template <class C> bool key_pairing(const char* dir) {
   return ok;
 }
 
-int main() {
+// ---- case files (tests/test_pairing_designed_cpu.py) --------------------------------------------------------------------------------
+// host_pairing_check cases <in> <out>: the operations of mnt753_test_tower_op and mnt753_test_miller_loop through the one-lane fields.
+// in:  u64 curve (0 / 1) | u64 op | u64 n | the operands in wire words: a[n] then b[n] tower elements for the tower ops (op 0 a b,
+//      1 a^2, 2 a^-1, 3 the unitary inverse, 4 a^|w0|, 5 the final exponentiation, 10 + i a^(q^i)), or g1[n] then g2[n] affine
+//      points for op 20, the unreduced Miller value.
+// out: n tower elements in wire words.
+template <class F> void f_load(typename F::E& r, const uint64_t* w) {
+  for (int k = 0; k < F::DEG; ++k) fp_from_wire(F::comp(r, k), (const uint32_t*)(w + 12 * k));
+}
+
+template <class C> bool run_cases(uint64_t op, size_t n, const std::vector<uint64_t>& in, std::vector<uint64_t>& out) {
+  using F = typename C::F;
+  using A = Ate<C>;
+  using T = Tower<F>;
+  constexpr int D = F::DEG, WT = 24 * D;
+  const bool miller = op == 20;
+  if (!(op <= 5 || (op >= 11 && op < 10 + (uint64_t)T::K) || miller)) { printf("cases: unknown op %llu\n", (unsigned long long)op); return false; }
+  const size_t wa = miller ? 24 : WT, wb = miller ? 24 * D : WT;
+  if (in.size() != 3 + n * (wa + wb)) { printf("cases: %zu words for n = %zu of op %llu\n", in.size(), n, (unsigned long long)op); return false; }
+  const uint64_t *pa = in.data() + 3, *pb = pa + n * wa;
+  out.assign(n * WT, 0);
+  for (size_t t = 0; t < n; ++t) {
+    typename T::E a, b, r;
+    if (miller) {
+      typename A::B px, py;
+      typename A::FE qx, qy;
+      fp_from_wire(px, (const uint32_t*)(pa + t * wa));
+      fp_from_wire(py, (const uint32_t*)(pa + t * wa + 12));
+      f_load<F>(qx, pb + t * wb);
+      f_load<F>(qy, pb + t * wb + 12 * D);
+      typename A::Pair p[1];
+      A::setup(p[0], px, py, qx, qy);
+      A::template miller_loop<1>(r, p);
+    } else {
+      f_load<F>(a.c0, pa + t * WT); f_load<F>(a.c1, pa + t * WT + 12 * D);
+      f_load<F>(b.c0, pb + t * WT); f_load<F>(b.c1, pb + t * WT + 12 * D);
+      switch (op) {
+        case 0: T::mul(r, a, b); break;
+        case 1: T::sqr(r, a); break;
+        case 2: T::inv(r, a); break;
+        case 3: T::unitary_inverse(r, a); break;
+        case 4: T::pow(r, a, PAIRC[A::CURVE].w0_abs, PAIRC[A::CURVE].w0_bits); break;
+        case 5: A::final_exponentiation(r, a); break;
+        case 11: T::template frobenius<1>(r, a); break;
+        case 12: T::template frobenius<2>(r, a); break;
+        case 13: T::template frobenius<3>(r, a); break;
+        case 14: T::template frobenius<4>(r, a); break;
+        default: T::template frobenius<5>(r, a); break;
+      }
+    }
+    f_words<F>(out.data() + t * WT, r.c0);
+    f_words<F>(out.data() + t * WT + 12 * D, r.c1);
+  }
+  return true;
+}
+
+static int cases_main(const char* in_path, const char* out_path) {
+  FILE* f = fopen(in_path, "rb");
+  if (!f) { printf("no file %s\n", in_path); return 1; }
+  std::vector<uint64_t> in;
+  uint64_t buf[512];
+  size_t got;
+  while ((got = fread(buf, 8, 512, f)) > 0) in.insert(in.end(), buf, buf + got);
+  fclose(f);
+  if (in.size() < 3 || in[0] > 1 || in[2] > (1u << 20)) { printf("cases: bad header\n"); return 1; }
+  std::vector<uint64_t> out;
+  const bool ok = in[0] == 0 ? run_cases<Mnt4G2>(in[1], (size_t)in[2], in, out) : run_cases<Mnt6G2>(in[1], (size_t)in[2], in, out);
+  if (!ok) return 1;
+  FILE* o = fopen(out_path, "wb");
+  if (!o) { printf("cannot write %s\n", out_path); return 1; }
+  const size_t put = fwrite(out.data(), 8, out.size(), o);
+  if (fclose(o) != 0 || put != out.size()) { printf("short write to %s\n", out_path); return 1; }
+  printf("cases: %zu results\n", (size_t)in[2]);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc == 4 && strcmp(argv[1], "cases") == 0) return cases_main(argv[2], argv[3]);
+  if (argc != 1) { printf("usage: host_pairing_check [cases <in> <out>]\n"); return 2; }
   bool ok = true;
   ok &= tower_identities<Mnt4G2>("Fq4");
   ok &= tower_identities<Mnt6G2>("Fq6");
