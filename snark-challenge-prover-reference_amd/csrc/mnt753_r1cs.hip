@@ -97,6 +97,12 @@ __global__ void __launch_bounds__(256) k_r1cs_evaluate(const uint64_t* __restric
   const uint64_t* rp = which == 0 ? rp_a : (which == 1 ? rp_b : rp_c);
   const uint32_t* col = which == 0 ? col_a : (which == 1 ? col_b : col_c);
   const uint32_t* cf = which == 0 ? cf_a : (which == 1 ? cf_b : cf_c);
+  // The range of the lazy sum.  c is what k_coeff_to_internal stored (fp_from_wire: < 2r), x a canonical wire integer (< r), so by fp_mul's
+  // contract p < r (2r / 2^756 + 1) < 1.2211 r with normalised limbs.  Before an fp_norm the accumulator holds a flushed value
+  // (< 1.51 r) and two products: < 3.9522 r, limbs < 3 2^28, |q| <= 3 -- inside fp_norm's contract (|value| < 5 r, |limb| + 2^28 |q| <
+  // 2^31 - 2^4).  tools/host_r1cs_check.cpp is this loop compiled for the host -- THE TWO MIRROR EACH OTHER, change them together -- and
+  // asserts those bounds after every step on every pair of the designed operands of tests/r1cs_designed.py; the largest it saw:
+  // product 1.027 r (MNT4753) / 1.103 r (MNT6753), accumulator before fp_norm 3.443 r / 3.372 r, limb 3.000 2^28, |q| 2.
   Fp<M> acc, c, x, p;
   fp_zero(acc);
   uint32_t pending = 0;
@@ -104,10 +110,10 @@ __global__ void __launch_bounds__(256) k_r1cs_evaluate(const uint64_t* __restric
     load_wire24(wv, w_wire + 24 * (size_t)col[k]);
     fp_unpack(x, wv);                      // w R as an integer < r, 28-bit limbs
     fp_load(c, cf + k * FPS_WORDS);        // c R'
-    fp_mul(p, c, x);                       // c w R, lazily in [0, 2r)
+    fp_mul(p, c, x);                       // c w R, lazily in [0, 1.2211 r)
 #pragma unroll
     for (int i = 0; i < NL; ++i) acc.l[i] += p.l[i];
-    if (++pending == 2u) { fp_norm(acc, acc); pending = 0; }   // value < 1.51 r + 2 * 2r: inside fp_norm's range
+    if (++pending == 2u) { fp_norm(acc, acc); pending = 0; }   // value < 1.51 r + 2 * 1.2211 r: inside fp_norm's range
   }
   if (pending) fp_norm(acc, acc);
   Fp<M> canon;

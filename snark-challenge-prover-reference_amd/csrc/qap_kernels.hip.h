@@ -173,10 +173,13 @@ __global__ void __launch_bounds__(256) k_qap_chunks(QapMatrices mats, const uint
     load_wire24(wv, u_wire + 24 * (size_t)perm_row[j]);
     fp_unpack(x, wv);                                        // u R as an integer < r
     fp_load(c, cf + (size_t)perm_k[j] * FPS_WORDS);          // c R'
-    fp_mul(p, c, x);                                         // c u R, lazily in [0, 2r)
+    fp_mul(p, c, x);                                         // c u R, lazily in [0, 1.2211 r): c < 2r, x < r (fp_mul's contract)
 #pragma unroll
     for (int i = 0; i < NL; ++i) acc.l[i] += p.l[i];
-    if (++pending == 2u) { fp_norm(acc, acc); pending = 0; } // value < 1.51 r + 2 * 2r: inside fp_norm's range
+    // a flushed value and two products: < 1.51 r + 2 * 1.2211 r = 3.9522 r, limbs < 3 2^28, |q| <= 3 -- inside fp_norm's contract.  The
+    // loop of k_r1cs_evaluate (csrc/mnt753_r1cs.hip) over u; tools/host_r1cs_check.cpp MIRRORS both (change them together) and asserts
+    // the bounds on the designed operands: largest product 1.027 r / 1.103 r (MNT4753 / MNT6753), largest accumulator 3.443 r / 3.372 r
+    if (++pending == 2u) { fp_norm(acc, acc); pending = 0; }
   }
   if (pending) fp_norm(acc, acc);
   fp_store(partial + (size_t)chunk * FPS_WORDS, acc);
@@ -203,6 +206,9 @@ __global__ void __launch_bounds__(256) k_qap_fold(const uint32_t* __restrict__ p
     fp_load(x, partial + (size_t)j * FPS_WORDS);             // [0.49 r, 1.51 r)
 #pragma unroll
     for (int i = 0; i < NL; ++i) acc.l[i] += x.l[i];
+    // a flushed value (or the seed, < r) and two partial sums: < 3 * 1.51 r = 4.53 r, limbs < 3 2^28, |q| <= 4 -- inside fp_norm's
+    // contract (|value| < 5 r, |limb| + 2^28 |q| < 2^31 - 2^4), with less room than the term loops have.  tools/host_r1cs_check.cpp
+    // MIRRORS this loop (change them together); the largest it saw: 4.266 r / 4.494 r (MNT4753 / MNT6753), limb 3.000 2^28, |q| 3
     if (++pending == 2u) { fp_norm(acc, acc); pending = 0; }
   }
   if (pending) fp_norm(acc, acc);
