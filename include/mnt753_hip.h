@@ -511,7 +511,11 @@ size_t mnt753_vk_num_inputs(const mnt753_vk* vk);
 size_t mnt753_vk_coefficient_bytes(const mnt753_vk* vk);   /* device memory of the stored coefficients of the key's two G2 points */
 /* The device memory a mnt753_groth16_verify call on this key may allocate for a chunk of proofs, in bytes: the batch runs in chunks of
  * cap / (194 + 96 num_inputs) proofs (host-memory batches: 8 proof words + 96 num_inputs more per proof for the staged copy), at
- * least one and at most 2^16.  0 (the default): chunks of 2^16 proofs. */
+ * least one and at most 2^16.  0 (the default): chunks of 2^16 proofs.  mnt753_groth16_verify_folded_locate runs chunks of WHOLE
+ * segments (128 / 84 proofs), at least one segment, after what it keeps per segment of the call has come off the cap: (cap - segments
+ * per_segment) / (g per_proof) segments per chunk, per_proof = 546 (+ 96 (num_inputs + 1) with public inputs, + the staged copy of a
+ * host batch), per_segment = 516 + g + 96 (num_inputs + 1) + one GT element in device form (448 / 672 bytes) (+ 336 (slices + 1) + 112
+ * with a prepared key); see that call's comment. */
 int mnt753_vk_set_workspace_cap(mnt753_vk* vk, size_t bytes);
 /* alpha_g1_beta_g2 of the key, mnt753_gt_words words */
 int mnt753_vk_gt(const mnt753_vk* vk, uint64_t* out);
@@ -604,6 +608,43 @@ int mnt753_groth16_verify_ex(const mnt753_vk* vk, const uint64_t* proofs, const 
  * 128 (MNT6753: 84) proofs.  Blocks until the verdict is there. */
 int mnt753_groth16_verify_folded(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int on_device,
                                  const uint64_t* coefficients /* n x 2 words, host */, uint8_t* status /* n, host, may be NULL */, int* accepted, void* stream);
+/* The fold that names the wrong proofs: one tail per SEGMENT.  A segment is one workgroup of the fold's Miller
+ * kernel: mnt753_fold_segment_proofs(curve) = 128 (MNT4753) or 84 (MNT6753) consecutive proofs, segment s holding the proofs
+ * [s g, min(n, (s + 1) g)); 0 for an unknown curve.  With the rho_i of the caller as for mnt753_groth16_verify_folded, segment s has
+ *     F_s = prod ML(rho_i A_i, B_i),  T_s = sum rho_i C_i,  rho_s = sum rho_i (< 2^135),  c_js = sum rho_i x_ij mod r,
+ *     S_s = rho_s ABC[0] + sum_j c_js ABC[j + 1]        (products and sums over the proofs i of the segment)
+ * and is accepted iff none of its proofs has a status (1 or 3) and FE(F_s ML(-S_s, G2::one()) ML(-T_s, delta_g2)) ==
+ * alpha_g1_beta_g2^rho_s: the equation and the soundness statement of mnt753_groth16_verify_folded on the segment, 2^-128 per segment
+ * and a union bound over the segments of a call.  There is no global F, T or tail: all segment tails of a call run side by side in one launch, one
+ * lane group each.  A segment that is not accepted is handed WHOLE to the per-proof verifier, mnt753_groth16_verify_ex with
+ * MNT753_VERIFY_CHECK_SUBGROUP (adjacent rejected segments as one range), and its proofs get that verifier's bytes; the proofs of an
+ * accepted segment get 0.
+ * verdicts (host memory, n bytes, REQUIRED): 0, 1, 2, 3 as for mnt753_groth16_verify_ex.  Returns the number of proofs not accepted
+ * (>= 0) or a negative code, as mnt753_groth16_verify does; n = 0 returns 0.  Arguments, device rules and errors are those of
+ * mnt753_groth16_verify_folded: MNT753_EINVAL for a null pointer, a zero coefficient, n > 2^24 or memory on another device.
+ * Two things to know.  (1) The one semantic difference inherited from the fold: inside an ACCEPTED segment acc_i is never formed, so
+ * "acc_i is the identity" is not reported there (a rechecked segment reports it, as the per-proof verifier does).  (2) A segment that
+ * contains a proof with a status is rechecked whole; the flagged proof is not masked out of rho_s and c_js, so its neighbours in the
+ * segment pay the per-proof pass as well.
+ * Chunks: a chunk is a whole number of segments and at least one, at most 2^16 proofs rounded down to whole segments.  The scaling,
+ * the point sums, the Miller loops and the segment scalars run per chunk; what they leave per SEGMENT is kept for the whole call, and
+ * S_s and the tails of ALL segments of the call then run in one launch each.  Under mnt753_vk_set_workspace_cap a proof of a chunk
+ * takes 546 bytes (with public inputs 96 (num_inputs + 1) more, plus its staged copy if it arrives in host memory); a segment of the
+ * CALL takes one GT element in device form (448 / 672 bytes), 192 + 192 bytes for S_s and T_s, 32 + 96 for rho_s, 4 for its verdict,
+ * 128 / 84 status bytes, 96 (num_inputs + 1) for the scalars of S_s, and with a prepared key the 336 (slices + 1) + 112 bytes of its
+ * walk.  The segments' share comes off the cap first, the rest bounds the chunk; a cap below that still runs one segment per chunk.
+ * The recheck allocates as mnt753_groth16_verify_ex does, under the same cap, before the fold's buffers are freed.  Rejected segments
+ * that are not all adjacent are gathered into ONE batch for it (a copy of their proofs and inputs, 8 proof words + 96 num_inputs bytes
+ * per rechecked proof, on the device for a device batch and in host memory for a host batch): a call of the per-proof verifier is one
+ * serial chain deep whatever its size.  Where a cap is set and that copy would exceed it, every run is verified where it lies instead.
+ * report (may be NULL): the segments of the call, how many were rejected, how many proofs the per-proof verifier rechecked, and the
+ * milliseconds on the device of the scaling with the point sums, the Miller loops, the segment scalars / S_s / tails, and (host clock)
+ * of the recheck.  Blocks until verdicts is complete. */
+size_t mnt753_fold_segment_proofs(int curve);
+typedef struct { uint64_t segments, segments_rejected, proofs_rechecked; float ms_scale, ms_miller, ms_tails, ms_recheck; } mnt753_fold_locate_report;
+int mnt753_groth16_verify_folded_locate(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int on_device,
+                                        const uint64_t* coefficients /* n x 2 words, host */, uint8_t* verdicts /* n, host, required */,
+                                        mnt753_fold_locate_report* report /* may be NULL */, void* stream);
 
 /* ---- input validation (device) --------------------------------------------------------------------------
  * The reference prover trusts its files (unchecked fread, prover_reference_functions.cpp:48-116); what the reference HAS for the

@@ -85,6 +85,18 @@ int mnt753_test_g2_loop_multiple(int curve, const uint64_t* g2_affine, size_t n,
  * filled whatever the verdict. */
 int mnt753_test_fold_parts(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, const uint64_t* coefficients, uint64_t* out_f,
                            uint64_t* out_s, uint64_t* out_t, uint64_t* out_rho, uint8_t* status, int* accepted);
+/* mnt753_groth16_verify_folded_locate on host-memory proofs, inputs and coefficients with the parts of every SEGMENT handed out (host
+ * memory, any of the out_ pointers and status may be NULL), one entry per segment, ceil(n /
+ * mnt753_fold_segment_proofs(curve)) of them, in order: out_f the UNREDUCED product of the segment's stepped pairs' Miller values
+ * (mnt753_gt_words words each), out_s = S_s and out_t = T_s (affine wire form, 24 words each, the identity as zero words), out_rho =
+ * rho_s as an element of Fr (wire form, 12 words each), out_accepted the segment tail's answer (1 byte each: 1 accepted).  status: the
+ * fold's status byte of every proof (n bytes: 0, 1, 3).  verdicts (n bytes, required), report and the return value as for the call
+ * itself.  The parts are filled whatever the verdicts. */
+int mnt753_test_fold_segment_parts(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, const uint64_t* coefficients, uint64_t* out_f,
+                                   uint64_t* out_s, uint64_t* out_t, uint64_t* out_rho, uint8_t* out_accepted, uint8_t* status, uint8_t* verdicts,
+                                   mnt753_fold_locate_report* report);
+/* chunks the calling thread's last mnt753_groth16_verify_folded_locate / mnt753_test_fold_segment_parts ran */
+size_t mnt753_test_fold_locate_last_chunks(void);
 /* milliseconds on the device (HIP events) of the stages of the calling thread's last mnt753_groth16_verify_folded / mnt753_test_fold_parts:
  * [0] the scaling and the point sum, [1] the Miller loops and the products, [2] the tail (0 where it was skipped).  tools/bench_fold.py. */
 int mnt753_test_fold_last_timing(float out_ms[3]);

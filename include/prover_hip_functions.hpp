@@ -206,6 +206,16 @@ public:
   };
   static folded_verdict verify_folded(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *proofs, const uint64_t *inputs, size_t n,
                                       const uint64_t *coefficients);
+  // the fold with one tail per segment (mnt753_groth16_verify_folded_locate): the verdicts of verify(.., true),
+  // with the per-proof pass run on the rejected segments only (segments of mnt753_fold_segment_proofs(curve) proofs); coefficients as
+  // for verify_folded
+  struct fold_locate_report { uint64_t segments, segments_rejected, proofs_rechecked; float ms_scale, ms_miller, ms_tails, ms_recheck; };
+  struct located_verdicts {
+    std::vector<uint8_t> verdicts;
+    fold_locate_report report;
+  };
+  static located_verdicts verify_folded_locate(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *proofs, const uint64_t *inputs, size_t n,
+                                               const uint64_t *coefficients);
   // Compressed points (mnt753_compress_points / mnt753_decompress_points / mnt753_groth16_verify_compressed):
   // x and one flag byte per point -- bit 0 the parity of y as an integer, bit 1 the identity.  group: MNT753_G1 / MNT753_G2; wire words
   // in host memory.  compress_points validates nothing; decompress_points reports like a check (entry "points"), a bad point's words
@@ -238,6 +248,8 @@ public:
                                      bool check_subgroup, const input_tables &tables);
   static folded_verdict verify_folded(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *proofs, const uint64_t *inputs, size_t n,
                                       const uint64_t *coefficients, const input_tables &tables);
+  static located_verdicts verify_folded_locate(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *proofs, const uint64_t *inputs, size_t n,
+                                               const uint64_t *coefficients, const input_tables &tables);
   static std::vector<uint8_t> verify_compressed(const uint64_t *vk_elements, size_t num_inputs, const uint64_t *x, const uint8_t *flags, const uint64_t *inputs,
                                                 size_t n, bool check_subgroup, const input_tables &tables);
   // raw access for tests / tools

@@ -13,7 +13,7 @@ from .api import (  # noqa: F401
     check_points, check_scalars, check_products, CheckReport, BAD_NONE, BAD_NONCANONICAL, BAD_OFF_CURVE, BAD_UNSATISFIED, FixedBase,
     vec_powers, vec_dot, poly_eval, HCheckResult, QapPlan, generate, GeneratedKey, write_r1cs_file, group_generator, compact_nonzero, scatter_rows, keygen_combine,
     pairing, gt_words, VerificationKey, check_subgroup, BAD_NOT_IN_SUBGROUP, VERIFY_CHECK_SUBGROUP,
-    compressed_words, compress_points, decompress_points, points_to_stream, points_from_stream,
+    compressed_words, compress_points, decompress_points, points_to_stream, points_from_stream, fold_segment_proofs,
 )
 from . import parallel  # noqa: F401,E402
 from . import api  # noqa: F401,E402

@@ -69,6 +69,17 @@ class HCheckResult(C.Structure):
     _fields_ = [("ok", C.c_int32), ("reserved", C.c_int32), ("lhs", C.c_uint64 * 12), ("rhs", C.c_uint64 * 12)]
 
 
+class FoldLocateReport(C.Structure):
+    """mnt753_fold_locate_report"""
+    _fields_ = [("segments", C.c_uint64), ("segments_rejected", C.c_uint64), ("proofs_rechecked", C.c_uint64), ("ms_scale", C.c_float),
+                ("ms_miller", C.c_float), ("ms_tails", C.c_float), ("ms_recheck", C.c_float)]
+
+    def as_dict(self):
+        return {"segments": int(self.segments), "segments_rejected": int(self.segments_rejected), "proofs_rechecked": int(self.proofs_rechecked),
+                "ms_scale": float(self.ms_scale), "ms_miller": float(self.ms_miller), "ms_tails": float(self.ms_tails),
+                "ms_recheck": float(self.ms_recheck)}
+
+
 # Names an OLDER build of the library may lack: empty in the product.  An A/B tool that times a build from before a call existed
 # (tools/bench_fold.py with MNT753_LIB) adds the name here before the first lib(); every other name must resolve.
 OPTIONAL_SYMBOLS = set()
@@ -203,6 +214,8 @@ def lib():
         "mnt753_groth16_verify": (i, [vp, vp, vp, sz, i, vp, vp]),
         "mnt753_groth16_verify_ex": (i, [vp, vp, vp, sz, i, C.c_uint, vp, vp]),
         "mnt753_groth16_verify_folded": (i, [vp, vp, vp, sz, i, u64p, vp, C.POINTER(C.c_int), vp]),
+        "mnt753_fold_segment_proofs": (sz, [i]),
+        "mnt753_groth16_verify_folded_locate": (i, [vp, vp, vp, sz, i, u64p, vp, C.POINTER(FoldLocateReport), vp]),
         "mnt753_compressed_words": (sz, [i, i]),
         "mnt753_compress_points": (i, [i, i, vp, i, sz, vp, vp, vp]),
         "mnt753_decompress_points": (i, [i, i, vp, vp, i, sz, vp, C.POINTER(CheckReport), vp]),
@@ -253,6 +266,9 @@ def test_lib():
         "mnt753_test_g2_loop_multiple": (i, [i, u64p, sz, u64p]),
         "mnt753_test_reduce_capped": (i, [i, i, C.c_void_p, C.c_void_p, sz, u64p, C.c_uint, u64p]),
         "mnt753_test_fold_parts": (i, [C.c_void_p, u64p, u64p, sz, u64p, u64p, u64p, u64p, u64p, C.c_void_p, C.POINTER(C.c_int)]),
+        "mnt753_test_fold_segment_parts": (i, [C.c_void_p, u64p, u64p, sz, u64p, u64p, u64p, u64p, u64p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(FoldLocateReport)]),
+        "mnt753_test_fold_locate_last_chunks": (C.c_size_t, []),
         "mnt753_test_fold_last_timing": (i, [C.POINTER(C.c_float)]),
         "mnt753_test_vk_force_inputs_per_lane": (i, [C.c_void_p, C.c_uint32]),
         "mnt753_test_vk_inputs_last_timing": (i, [C.c_void_p, C.POINTER(C.c_float)]),
@@ -1410,6 +1426,42 @@ class VerificationKey:
                                                  C.c_void_p(status.ctypes.data), C.byref(accepted)), "mnt753_test_fold_parts")
         return {"f": f, "s": s, "t": t, "rho": rho, "status": status, "accepted": bool(accepted.value)}
 
+    def verify_folded_locate(self, proofs, inputs, coefficients=None, on_device=False, n=None, stream=None):
+        """mnt753_groth16_verify_folded_locate: the fold with one tail per segment of fold_segment_proofs(curve) proofs (DESIGN.md
+        section 4.18) -> (verdicts [n] as verify(.., check_subgroup=True), report dict: segments, segments_rejected, proofs_rechecked,
+        ms_scale, ms_miller, ms_tails, ms_recheck).  Only the rejected segments pay the per-proof pass.  coefficients as for
+        verify_folded(): None draws them from `secrets`."""
+        pp, pi, cnt, co, keep = self._fold_args(proofs, inputs, coefficients, on_device, n)
+        verdicts = np.zeros(cnt, dtype=np.uint8)
+        rep = FoldLocateReport()
+        st = C.c_void_p(int(stream)) if stream else C.c_void_p()
+        rc = lib().mnt753_groth16_verify_folded_locate(self._h, pp, pi, cnt, 1 if on_device else 0, co.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                       C.c_void_p(verdicts.ctypes.data), C.byref(rep), st)
+        if rc < 0:
+            _check(rc, "mnt753_groth16_verify_folded_locate")
+        return verdicts, rep.as_dict()
+
+    def test_fold_segment_parts(self, proofs, inputs, coefficients):
+        """mnt753_test_fold_segment_parts (test library) on host arrays -> dict, one row per segment: f [segments, gt_words] (the
+        unreduced products), s, t [segments, 24] (affine wire form), rho [segments, 12] (Fr wire form), accepted [segments]; status
+        and verdicts [n]; report"""
+        pp, pi, cnt, co, keep = self._fold_args(proofs, inputs, coefficients, False, None)
+        u64p = C.POINTER(C.c_uint64)
+        g = fold_segment_proofs(self.curve)
+        segs = (cnt + g - 1) // g
+        f, s, t, rho = (np.zeros((segs, k), dtype=np.uint64) for k in (gt_words(self.curve), 24, 24, 12))
+        accepted = np.zeros(segs, dtype=np.uint8)
+        status = np.zeros(cnt, dtype=np.uint8)
+        verdicts = np.zeros(cnt, dtype=np.uint8)
+        rep = FoldLocateReport()
+        rc = test_lib().mnt753_test_fold_segment_parts(self._h, C.cast(pp, u64p), C.cast(pi, u64p), cnt, co.ctypes.data_as(u64p), f.ctypes.data_as(u64p),
+                                                       s.ctypes.data_as(u64p), t.ctypes.data_as(u64p), rho.ctypes.data_as(u64p),
+                                                       C.c_void_p(accepted.ctypes.data), C.c_void_p(status.ctypes.data),
+                                                       C.c_void_p(verdicts.ctypes.data), C.byref(rep))
+        if rc < 0:
+            _check(rc, "mnt753_test_fold_segment_parts")
+        return {"f": f, "s": s, "t": t, "rho": rho, "accepted": accepted, "status": status, "verdicts": verdicts, "report": rep.as_dict()}
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib().mnt753_vk_destroy(self._h)
@@ -1420,6 +1472,16 @@ class VerificationKey:
             self.close()
         except Exception:
             pass
+
+
+def fold_segment_proofs(curve):
+    """mnt753_fold_segment_proofs: proofs per segment of verify_folded_locate() -- 128 (MNT4753) or 84 (MNT6753)"""
+    return int(lib().mnt753_fold_segment_proofs(curve))
+
+
+def test_fold_locate_last_chunks():
+    """mnt753_test_fold_locate_last_chunks (test library): chunks the last verify_folded_locate / test_fold_segment_parts ran"""
+    return int(test_lib().mnt753_test_fold_locate_last_chunks())
 
 
 def test_fold_last_timing():

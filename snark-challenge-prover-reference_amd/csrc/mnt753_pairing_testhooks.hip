@@ -8,6 +8,7 @@
 #include "common_host.hpp"
 #include "../../include/mnt753_hip_test.h"
 #include "fold_api.hpp"
+#include "fold_locate_api.hpp"
 #include "pairing_kernels.hip.h"
 #include "vk_inputs_api.hpp"
 
@@ -129,6 +130,14 @@ extern "C" int mnt753_test_fold_parts(const mnt753_vk* vk, const uint64_t* proof
   parts.f = out_f; parts.s = out_s; parts.t = out_t; parts.rho = out_rho;
   return groth16_verify_folded_parts(vk, proofs, inputs, n, 0, coefficients, status, accepted, nullptr, &parts);
 }
+extern "C" int mnt753_test_fold_segment_parts(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, const uint64_t* coefficients,
+                                              uint64_t* out_f, uint64_t* out_s, uint64_t* out_t, uint64_t* out_rho, uint8_t* out_accepted, uint8_t* status,
+                                              uint8_t* verdicts, mnt753_fold_locate_report* report) {
+  FoldLocateParts parts;
+  parts.f = out_f; parts.s = out_s; parts.t = out_t; parts.rho = out_rho; parts.accepted = out_accepted; parts.status = status;
+  return groth16_verify_folded_locate_parts(vk, proofs, inputs, n, 0, coefficients, verdicts, report, nullptr, &parts);
+}
+extern "C" size_t mnt753_test_fold_locate_last_chunks(void) { return groth16_fold_locate_last_chunks(); }
 extern "C" int mnt753_test_fold_last_timing(float out_ms[3]) {
   if (!out_ms) return set_error(MNT753_EINVAL, "test_fold_last_timing: bad argument");
   groth16_fold_last_timing(out_ms);

@@ -612,7 +612,7 @@ static bool fold_coefficients(const char* path, size_t n, std::vector<uint64_t>&
   return true;
 }
 struct VerifyOptions {
-  bool check_subgroup = false, fold = false, compressed = false, input_tables = false, quiet = false;
+  bool check_subgroup = false, fold = false, fold_locate = false, compressed = false, input_tables = false, quiet = false;
   int input_window_bits = 0;   // --input-window-bits: 0 leaves the width to the library
   const char* fold_file = nullptr;
 };
@@ -732,15 +732,19 @@ static int verify_batch(const VerifyOptions& vo, const std::vector<uint64_t>& el
       fprintf(stderr, "main_hip: %s of the key: %s\n", e.first_bad == 0 ? "beta_g2" : "delta_g2", B::check_reason_text(e.reason));
       return 3;
     }
-    if (vo.fold) {
-      const bool accepted = B::verify_folded(el.data(), num_inputs, proofs.data(), per_proof.data(), n, coef.data(), tp.tables).accepted;
+    if (vo.fold_locate) {
+      // --fold-locate: one tail per segment; only the rejected segments pay the per-proof pass
+      const auto located = B::verify_folded_locate(el.data(), num_inputs, proofs.data(), per_proof.data(), n, coef.data(), tp.tables);
+      fprintf(stderr, "fold: %llu segments, %llu rejected, %llu proofs rechecked\n", (unsigned long long)located.report.segments,
+              (unsigned long long)located.report.segments_rejected, (unsigned long long)located.report.proofs_rechecked);
+      verdicts = located.verdicts;
+    } else if (vo.fold && B::verify_folded(el.data(), num_inputs, proofs.data(), per_proof.data(), n, coef.data(), tp.tables).accepted) {
       tp.print(vo);
-      if (accepted) {
-        printf("VERIFIED %zu proofs (folded)\n", n);
-        return 0;
-      }
+      printf("VERIFIED %zu proofs (folded)\n", n);
+      return 0;
+    } else {                                       // --check-subgroup alone, or a fold that rejected: the per-proof pass names the proofs
+      verdicts = B::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n, true, tp.tables);
     }
-    verdicts = B::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n, true, tp.tables);
   } else {
     verdicts = B::verify(el.data(), num_inputs, proofs.data(), per_proof.data(), n, false, tp.tables);
   }
@@ -779,7 +783,7 @@ static int verify_proofs(int curve, const std::vector<const char*>& pos, const V
     if (one.size() != 48 + w2) { fprintf(stderr, "main_hip: %s is not a proof A | B | C\n", pos[k]); return 3; }
     proofs.insert(proofs.end(), one.begin(), one.end());
   }
-  if (vo.fold && !fold_coefficients(vo.fold_file, n, coef)) return 1;
+  if ((vo.fold || vo.fold_locate) && !fold_coefficients(vo.fold_file, n, coef)) return 1;
   if (mnt753_init(0) != 0) { fprintf(stderr, "main_hip: %s\n", mnt753_last_error()); return 1; }
   std::vector<uint64_t> per_proof;
   for (size_t k = 0; k < n; ++k) per_proof.insert(per_proof.end(), inputs.begin() + 12, inputs.end());
@@ -873,13 +877,16 @@ static const char check_usage[] =
     "usage: %s MNT4753|MNT6753 check <params> [<input>] [--subgroup] [--gpus N]\n       %s MNT4753|MNT6753 check-r1cs <params> <r1cs> <witness> [--gpus N]\n"
     "  --subgroup: the B2 points must also lie in G2, the order-r subgroup of the twist (\"not in the subgroup\")\n";
 static const char vk_usage[] =
-    "usage: %s MNT4753|MNT6753 vk <vk_elements.bin> <out>\n       %s MNT4753|MNT6753 verify <vk_elements.bin> <input_or_witness> <proof> [<proof> ...] [--check-subgroup] [--fold [--fold-coefficients <file>]] [--compressed] [--input-tables [--input-window-bits w]] [--quiet]\n"
+    "usage: %s MNT4753|MNT6753 vk <vk_elements.bin> <out>\n       %s MNT4753|MNT6753 verify <vk_elements.bin> <input_or_witness> <proof> [<proof> ...] [--check-subgroup] [--fold | --fold-locate [--fold-coefficients <file>]] [--compressed] [--input-tables [--input-window-bits w]] [--quiet]\n"
     "  vk: writes the complete verification key (with the GT element e(alpha_g1, beta_g2)) in the reference's vk.txt format.\n"
     "  verify: prints VERIFIED or REJECTED per proof; exit code 0 if every proof is accepted, 3 otherwise.\n"
     "  --check-subgroup: beta_g2 and delta_g2 of the key and B of every proof must lie in G2, the order-r subgroup of the twist;\n"
     "    a key that fails is named and nothing is verified (exit 3), such a proof prints REJECTED (B not in the subgroup).\n"
     "  --fold: the batch under one final exponentiation first (random coefficients, or n x 16 bytes from --fold-coefficients);\n"
     "    accepted: one line naming the count, exit 0; rejected: the per-proof lines of --check-subgroup, exit 3.\n"
+    "  --fold-locate: one folded check per segment of 128 (MNT6753: 84) proofs, the per-proof pass on the rejected segments only\n"
+    "    (coefficients as for --fold; implies --check-subgroup): the per-proof lines of --check-subgroup, and on stderr one line\n"
+    "    \"fold: <segments> segments, <rejected> rejected, <rechecked> proofs rechecked\"; exit 0 or 3.  Not with --fold or --compressed.\n"
     "  --compressed: the proof files are libff's compressed streams (compress-proof); a proof that does not decompress prints\n"
     "    REJECTED (malformed).  Not with --fold.\n"
     "  --input-tables: the key is prepared before it verifies -- one window table per ABC point, W = ceil(754 / w) additions per public\n"
@@ -1042,7 +1049,7 @@ static int vk_command(const Command& self, Options&, int argc, char** argv) {
   const int curve = parse_curve(argv[1]);
   if (curve < 0) return unknown_curve(argv[1]);
   std::vector<Flag> flags;
-  if (verify) flags = {{"--check-subgroup", false}, {"--fold", false}, {"--fold-coefficients", true}, {"--compressed", false},
+  if (verify) flags = {{"--check-subgroup", false}, {"--fold", false}, {"--fold-locate", false}, {"--fold-coefficients", true}, {"--compressed", false},
                        {"--input-tables", false}, {"--input-window-bits", true}, {"--quiet", false}};
   ArgScan a{argc, argv, 3, flags};
   std::vector<const char*> pos;
@@ -1051,6 +1058,7 @@ static int vk_command(const Command& self, Options&, int argc, char** argv) {
     if (a.is("--check-subgroup")) vo.check_subgroup = true;
     else if (a.is("--compressed")) vo.compressed = true;
     else if (a.is("--fold")) vo.fold = vo.check_subgroup = true;
+    else if (a.is("--fold-locate")) vo.fold_locate = vo.check_subgroup = true;
     else if (a.is("--fold-coefficients")) vo.fold_file = a.value;
     else if (a.is("--input-tables")) vo.input_tables = true;
     else if (a.is("--quiet")) vo.quiet = true;
@@ -1064,6 +1072,8 @@ static int vk_command(const Command& self, Options&, int argc, char** argv) {
   }
   if (a.refused) return 2;
   if (verify ? pos.size() < 3 : pos.size() != 2) return usage(self.usage, argv[0]);
+  if (vo.fold_locate && vo.fold) { fprintf(stderr, "main_hip: --fold-locate and --fold are two verifiers: name one\n"); return 2; }
+  if (vo.fold_locate && vo.compressed) { fprintf(stderr, "main_hip: --fold-locate takes no compressed proofs\n"); return 2; }
   if (vo.compressed && vo.fold) { fprintf(stderr, "main_hip: --fold takes no compressed proofs\n"); return 2; }
   if (vo.input_window_bits && !vo.input_tables) { fprintf(stderr, "main_hip: --input-window-bits goes with --input-tables\n"); return 2; }
   return vk_or_verify(curve, verify, pos, vo);

@@ -1532,6 +1532,22 @@ template <int CURVE> typename HIP_B::folded_verdict HIP_B::verify_folded(const u
                                                                         size_t n, const uint64_t* coefficients) {
   return verify_folded(vk_elements, num_inputs, proofs, inputs, n, coefficients, input_tables{});
 }
+template <int CURVE> typename HIP_B::located_verdicts HIP_B::verify_folded_locate(const uint64_t* vk_elements, size_t num_inputs, const uint64_t* proofs,
+                                                                                  const uint64_t* inputs, size_t n, const uint64_t* coefficients,
+                                                                                  const input_tables& tables) {
+  CallKey key;
+  make_call_key<CURVE>(key, vk_elements, num_inputs, tables);
+  located_verdicts out{std::vector<uint8_t>(n), fold_locate_report{}};
+  mnt753_fold_locate_report r{};
+  const int rc = mnt753_groth16_verify_folded_locate(key.vk, proofs, inputs, n, 0, coefficients, out.verdicts.data(), &r, nullptr);
+  if (rc < 0) check(rc, "mnt753_groth16_verify_folded_locate");
+  out.report = fold_locate_report{r.segments, r.segments_rejected, r.proofs_rechecked, r.ms_scale, r.ms_miller, r.ms_tails, r.ms_recheck};
+  return out;
+}
+template <int CURVE> typename HIP_B::located_verdicts HIP_B::verify_folded_locate(const uint64_t* vk_elements, size_t num_inputs, const uint64_t* proofs,
+                                                                                  const uint64_t* inputs, size_t n, const uint64_t* coefficients) {
+  return verify_folded_locate(vk_elements, num_inputs, proofs, inputs, n, coefficients, input_tables{});
+}
 template <int CURVE> typename HIP_B::compressed_points HIP_B::compress_points(int group, const uint64_t* affine, size_t n) {
   compressed_points out{std::vector<uint64_t>(n * mnt753_compressed_words(CURVE, group)), std::vector<uint8_t>(n)};
   check(mnt753_compress_points(CURVE, group, affine, 0, n, out.x.data(), out.flags.data(), nullptr), "mnt753_compress_points");

@@ -403,6 +403,26 @@ int mnt753_groth16_verify_folded(const mnt753_vk* vk, const uint64_t* proofs, co
   *accepted = getenv("MNT753_STUB_REJECT") == nullptr;
   return 0;
 }
+// every segment that holds a rejected proof is "rechecked": the verdicts are mnt753_groth16_verify_ex's (MNT753_STUB_REJECT)
+size_t mnt753_fold_segment_proofs(int curve) { return curve == MNT753_CURVE_MNT4753 ? 128 : (curve == MNT753_CURVE_MNT6753 ? 84 : 0); }
+int mnt753_groth16_verify_folded_locate(const mnt753_vk* vk, const uint64_t* proofs, const uint64_t* inputs, size_t n, int od, const uint64_t* coefficients,
+                                        uint8_t* verdicts, mnt753_fold_locate_report* report, void* st) {
+  if (!vk || (n && (!proofs || !coefficients || !verdicts))) return fail(MNT753_EINVAL, "groth16_verify_folded_locate: bad argument");
+  touch_ro(coefficients, 2 * n);
+  for (size_t i = 0; i < n; ++i)
+    if (!(coefficients[2 * i] | coefficients[2 * i + 1])) return fail(MNT753_EINVAL, "groth16_verify_folded_locate: a coefficient is zero");
+  const int rc = mnt753_groth16_verify_ex(vk, proofs, inputs, n, od, MNT753_VERIFY_CHECK_SUBGROUP, verdicts, st);
+  if (rc < 0 || !report) return rc;
+  const size_t g = mnt753_fold_segment_proofs(vk->curve);
+  *report = mnt753_fold_locate_report{(n + g - 1) / g, 0, 0, 0.f, 0.f, 0.f, 0.f};
+  for (size_t s = 0; s * g < n; ++s) {
+    const size_t end = (s + 1) * g < n ? (s + 1) * g : n;
+    bool bad = false;
+    for (size_t i = s * g; i < end; ++i) bad |= verdicts[i] != 0;
+    if (bad) { ++report->segments_rejected; report->proofs_rechecked += end - s * g; }
+  }
+  return rc;
+}
 int mnt753_group_generator(int curve, int group, uint64_t* out) {
   if (curve < 0 || curve > 1 || (group != MNT753_G1 && group != MNT753_G2) || !out) return fail(MNT753_EINVAL, "group_generator: bad argument");
   for (size_t i = 0; i < mnt753_affine_words(curve, group); ++i) out[i] = 1 + i;
